@@ -11,6 +11,11 @@ independent -> weak scaling, no data-path collective); barrier + max over ranks 
 region.  Launched either by torch.distributed.run (RANK / WORLD_SIZE in the environment) or as
 `python bench.py --gpus N`, which starts the N ranks itself (spawn_ranks) before this process
 touches torch or the GPU.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's results if
+`--dump-outputs DIR` is given and prints the headline line.  `--full` adds everything else to
+that line afterwards: H2D rates, the per-stage and roofline tables, the Frame-side legs, the other
+BASELINE configs, the multi-GPU exchanges and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -250,6 +255,47 @@ EUROC_K = (458.654, 457.296, 367.215, 248.375)  # EuRoC cam0 fx fy cx cy
 EUROC_D = (-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05)
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much (float32 rows)
+KEYPOINT_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
+
+
+def dump_outputs(be, out_dir, n_pairs, rank=0, world=1, seed=0):
+    """--dump-outputs: what the last step left for its caller, as float32 .npy files in out_dir
+    (`<name>_rank<r>.npy` on ranks other than 0):
+      counts        [2 * n_pairs, 2]  keypoints and mono index of every image of the batch
+      sample_pairs  [S]               the stereo pairs whose rows follow: a fixed, seeded sample
+                                      (always with the first and the last pair) that keeps the
+                                      files under DUMP_BYTES; every pair when they all fit
+      keypoints     [sum n, 7]        cv::KeyPoint fields (KEYPOINT_FIELDS) of the sampled pairs'
+                                      images, left then right, pair after pair
+      descriptors   [sum n, 32]       their descriptor bytes
+      matches       [sum n_left, 4]   the pairs' kNN2 rows (idx1, dist1, idx2, dist2)
+    Every value is an integer below 2^24 or a float32, so float32 holds it exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    nk, mono = be.counts()
+    per_pair = 4 * (2 * (len(KEYPOINT_FIELDS) + 32) + 4) * max(int(nk.max()), 1)
+    S = max(1, min(n_pairs, (DUMP_BYTES // world - 8 * len(nk)) // per_pair))  # the ranks share the limit
+    if S < n_pairs:
+        rest = 1 + np.random.default_rng(seed).permutation(n_pairs - 2)[:max(S - 2, 0)]
+        sample = np.unique(np.concatenate([[0, n_pairs - 1][:S], rest])).astype(np.int64)
+    else:
+        sample = np.arange(n_pairs)
+    kps, descs, matches = [], [], []
+    for p in sample:
+        for i in (2 * p, 2 * p + 1):
+            k, d, _ = be.result(int(i))
+            kps.append(np.stack([k[f].astype(np.float32) for f in KEYPOINT_FIELDS], axis=1))
+            descs.append(d.astype(np.float32))
+        matches.append(np.stack(be.matches(int(p)), axis=1).astype(np.float32))
+    arrays = {"counts": np.stack([nk, mono], axis=1).astype(np.float32),
+              "sample_pairs": sample.astype(np.float32),
+              "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs),
+              "matches": np.concatenate(matches)}
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def cpu_baseline(w, h, nfeatures, seconds, map_points=3000):
     """The oracle (scalar C++ restatement of the reference CPU ORBextractor + BFMatcher), one
     thread, on a bounded sample of the same workload: pairs until `seconds` elapse."""
@@ -348,6 +394,12 @@ def main():
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--nfeatures", type=int, default=2000)
     ap.add_argument("--nlevels", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures: H2D rates, "
+                         "per-stage and roofline tables, the Frame-side legs, the other configs, the "
+                         "multi-GPU exchanges and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stereo", action="store_true", help="skip the ComputeStereoMatches leg")
@@ -362,6 +414,8 @@ def main():
                     help="CPU test of the launch / rendezvous / reduction path only: a host stand-in "
                          "(tests/bench_stub.py) replaces liborbgpu; the line says data: stub")
     args = ap.parse_args()
+    if args.dump_outputs and args.stub_gpu:
+        ap.error("--dump-outputs needs the GPU path (the stub computes nothing)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -401,10 +455,6 @@ def main():
                            height=H, max_images=2 * P)
     be.upload(imgs)  # PCIe upload: outside the timed region (inputs resident in HBM)
     be.synchronize()
-    h0 = time.perf_counter()  # the same upload timed alone, for the H2D-inclusive rate
-    be.upload(imgs)
-    be.synchronize()
-    h2d_s = time.perf_counter() - h0
     laps = np.zeros((2 * P, 2), np.int32)
 
     def step():
@@ -415,27 +465,10 @@ def main():
         step()
     be.synchronize()
     nk, _ = be.counts()
-    cand_per_img = float(be.candidate_counts().mean())
     feats_per_step = int(nk.sum())
     nq_per_step = int(sum(nk[2 * p] for p in range(P)))
     pairs_per_step = int(sum(int(nk[2 * p]) * int(nk[2 * p + 1]) for p in range(P)))
 
-    # 1. short untimed pass, every stage one whole-batch launch bracketed by HIP events -> per-stage
-    #    table and the dominant kernel; 2. the timed region (production sub-batch streams, one
-    #    launch per stream and stage) brackets only that kernel's launches, so event cost stays
-    #    small; their durations include whatever the other streams run beside them
-    be.set_profiling(True, serialize=True)
-    be.reset_stage_times()
-    for _ in range(3):
-        step()
-    be.synchronize()
-    stages_all = be.stage_times()
-    dom_name = max(stages_all, key=lambda k: stages_all[k][0]) if stages_all else None
-    if args.no_profile or dom_name is None:
-        be.set_profiling(False)
-    else:
-        be.set_profiling(True, stages=[dom_name])
-    be.reset_stage_times()
     barrier(dist)
     be.synchronize()
     if has_cuda:
@@ -449,6 +482,74 @@ def main():
     t1 = time.perf_counter()
     barrier(dist)
     elapsed = max_over_ranks(dist, t1 - t0)
+    if args.dump_outputs:
+        dump_outputs(be, args.dump_outputs, P, rank, world)
+
+    total_feats = sum_over_ranks(dist, feats_per_step * args.steps)
+    total_q = sum_over_ranks(dist, nq_per_step * args.steps)
+    total_pairs = sum_over_ranks(dist, pairs_per_step * args.steps)
+    mfeat = total_feats / elapsed / 1e6
+    mmatch = total_q / elapsed / 1e6
+    out = {
+        "metric": "Mfeatures/s extract + Mmatches/s BFMatch, 640x480 stereo 8-level pyr, 1/2/4/8 GPU",
+        "value": round(mfeat, 3),
+        "unit": "Mfeatures/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": ("stub (CPU test of the multi-rank path, no GPU work)" if args.stub_gpu else
+                 "synthetic seeded stereo frames (SURVEY §8d generator), resident in HBM"),
+        "ranks": [{"rank": r_, "device": d_, "pid": p_} for r_, d_, p_ in placement],
+        "backend": dist.get_backend() if dist is not None else None,
+        "config": {"workload": "C2 640x480 stereo, 8 levels x1.2, 2000 feat/frame, FAST 20/7, "
+                               "+ per-pair 2000x2000 Hamming kNN2 (left->right, all rows)",
+                   "pairs_per_gpu_per_step": P, "images_per_gpu_per_step": 2 * P,
+                   "parallelism": "frames sharded across %d GPU(s), replicas" % world},
+        "matches": {"value": round(mmatch, 3), "unit": "Mmatches/s",
+                    "gpairs_s": round(total_pairs / elapsed / 1e9, 3)},
+        "features_per_step_per_gpu": feats_per_step,
+        "full": bool(args.full),
+    }
+    if not args.full:  # the plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return 0
+
+    # --full: everything below runs after the headline's timed region and leaves it as it was
+    h0 = time.perf_counter()  # the batch upload timed alone, for the H2D-inclusive rate
+    be.upload(imgs)
+    be.synchronize()
+    h2d_s = time.perf_counter() - h0
+
+    cand_per_img = float(be.candidate_counts().mean())
+    # 1. short pass, every stage one whole-batch launch bracketed by HIP events -> per-stage table
+    #    and the dominant kernel; 2. the headline's steps once more (production sub-batch streams,
+    #    one launch per stream and stage) with only that kernel's launches bracketed: their
+    #    durations include whatever the other streams run beside them
+    be.set_profiling(True, serialize=True)
+    be.reset_stage_times()
+    for _ in range(3):
+        step()
+    be.synchronize()
+    stages_all = be.stage_times()
+    dom_name = max(stages_all, key=lambda k: stages_all[k][0]) if stages_all else None
+    if args.no_profile or dom_name is None:
+        be.set_profiling(False)
+    else:
+        be.set_profiling(True, stages=[dom_name])
+    be.reset_stage_times()
+    barrier(dist)
+    if not args.no_profile and dom_name is not None:
+        for _ in range(args.steps):
+            step()
+        be.synchronize()
     stages_timed = be.stage_times()
     be.set_profiling(False)
 
@@ -472,15 +573,10 @@ def main():
     p_el = max_over_ranks(dist, time.perf_counter() - p0)
     be.free_pinned()
 
-    total_feats = sum_over_ranks(dist, feats_per_step * args.steps)
-    total_q = sum_over_ranks(dist, nq_per_step * args.steps)
-    total_pairs = sum_over_ranks(dist, pairs_per_step * args.steps)
-    mfeat = total_feats / elapsed / 1e6
     # the PCIe-inclusive rate beside the resident one (never `value`)
     h2d_max = max_over_ranks(dist, h2d_s)
     h2d_serial = sum_over_ranks(dist, feats_per_step) / (elapsed / args.steps + h2d_max) / 1e6
     h2d_incl = total_feats / p_el / 1e6
-    mmatch = total_q / elapsed / 1e6
 
     # per-stage table from the serialized pass: each stage one whole-batch launch per step (one per
     # level for k_blur_resize), alone on the GPU, so its duration is the kernel's own and the
@@ -533,14 +629,16 @@ def main():
             row["Tops"] = round(16.0 * pairs_launch / (avg_ms * 1e-3) / 1e12, 2)
             row["frac_valu"] = round(row["Tops"] / VALU_PEAK_TOPS, 4)
         stage_rows[name] = row
-    # the dominant kernel: the largest serialized total; its timed-region (concurrent) launches
-    # were bracketed with HIP events on their own streams and sit beside the kernel-alone figure
+    # the dominant kernel: the largest serialized total; its concurrent launches (the timed steps
+    # run again) were bracketed with HIP events on their own streams and sit beside the
+    # kernel-alone figure
     dom = dom_name if dom_name in stage_rows else None
     if dom is not None and stages_timed.get(dom, (0, 0))[1] > 0 and "bytes_per_launch" in stage_rows[dom]:
         tms, tcnt = stages_timed[dom]
         tb = per_img[dom] * n_img / (tcnt / args.steps)
         stage_rows[dom]["concurrent"] = {
-            "source": "timed region, HIP events on the chunk streams (other chunks' stages run beside it)",
+            "source": "the timed steps run again, HIP events on the chunk streams (other chunks' stages run "
+                      "beside it)",
             "avg_us": round(tms / tcnt * 1e3, 2), "launches": tcnt, "bytes_per_launch": int(tb),
             "GBps": round(tb / (tms / tcnt * 1e-3) / 1e9, 1),
             "frac_hbm": round(tb / (tms / tcnt * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
@@ -1004,29 +1102,7 @@ def main():
                "search_by_projection_mmappoints_s": round(cb["sbp_mmp_s"], 5) if cb["sbp_mmp_s"] else None}
 
     if rank == 0:
-        out = {
-            "metric": "Mfeatures/s extract + Mmatches/s BFMatch, 640x480 stereo 8-level pyr, 1/2/4/8 GPU",
-            "value": round(mfeat, 3),
-            "unit": "Mfeatures/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": ("stub (CPU test of the multi-rank path, no GPU work)" if args.stub_gpu else
-                     "synthetic seeded stereo frames (SURVEY §8d generator), resident in HBM"),
-            "ranks": [{"rank": r_, "device": d_, "pid": p_} for r_, d_, p_ in placement],
-            "backend": dist.get_backend() if dist is not None else None,
-            "config": {"workload": "C2 640x480 stereo, 8 levels x1.2, 2000 feat/frame, FAST 20/7, "
-                                   "+ per-pair 2000x2000 Hamming kNN2 (left->right, all rows)",
-                       "pairs_per_gpu_per_step": P, "images_per_gpu_per_step": 2 * P,
-                       "parallelism": "frames sharded across %d GPU(s), replicas" % world},
-            "matches": {"value": round(mmatch, 3), "unit": "Mmatches/s",
-                        "gpairs_s": round(total_pairs / elapsed / 1e9, 3)},
-            "features_per_step_per_gpu": feats_per_step,
+        out.update({
             "h2d": {"ms_per_batch_upload": round(h2d_max * 1e3, 3),
                     "GBps": round(imgs.nbytes / h2d_max / 1e9, 2) if h2d_max > 0 else None,
                     "mfeatures_s_incl_upload": round(h2d_incl, 3),
@@ -1047,7 +1123,7 @@ def main():
             "wire": wire,
             "cross_camera": cross,
             "ingest_c4": ingest,
-        }
+        })
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -13,7 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_bench(n, extra=()):
+def _run_bench(n, extra=("--full",)):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                         "GROUP_RANK", "ORBGPU_BENCH_BACKEND")}
@@ -54,3 +54,13 @@ def test_bench_single_rank_no_spawn():
     line = _run_bench(1)
     assert line["n_gpus"] == 1 and line["backend"] is None and len(line["ranks"]) == 1
     assert line["cross_camera"] is None
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full the line carries the headline (the timed steps) and none of the side legs."""
+    line = _run_bench(1, extra=())
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Mfeatures/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u8" and "Mfeatures/s" in line["metric"]
+    for key in ("stages", "roofline", "cpu_baseline", "h2d", "other_configs", "cross_camera", "ingest_c4"):
+        assert key not in line, key

@@ -11,12 +11,12 @@ summ() {
 import json,sys;d=json.load(open(sys.argv[1]));oc=d.get('other_configs',{})
 print('%-22s C2 %.1f (%.4f ms)' % (sys.argv[2], d['value'], d['ms_per_step']), ' '.join('%s %.1f/%.4fms' % (k, v['mfeatures_s'], v['ms_per_step']) for k, v in sorted(oc.items())))" "$@"
 }
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 summ $O/bench.json default
 python3 -c "import json;d=json.load(open('$O/bench.json'));[print(k,v['avg_us'],v['launches']) for k,v in d['stages'].items()]"
 export ORBGPU_DIAGNOSTICS=1
 for tm in 0 64 256 100000; do
-  ORBGPU_TAIL_MIN=$tm timeout -k 10 300 python bench.py --no-cpu-baseline --no-stereo --no-grid --no-wire --no-sbp --no-profile > $O/tail_$tm.json 2> $O/tail_$tm.err || { tail -20 $O/tail_$tm.err; exit 1; }
+  ORBGPU_TAIL_MIN=$tm timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-stereo --no-grid --no-wire --no-sbp --no-profile > $O/tail_$tm.json 2> $O/tail_$tm.err || { tail -20 $O/tail_$tm.err; exit 1; }
   summ $O/tail_$tm.json "TAIL_MIN=$tm"
 done
 unset ORBGPU_DIAGNOSTICS

@@ -16,5 +16,5 @@ if [ -n "$VTESTS" ]; then  # parity of each variant build on the named tests (a 
 fi
 timeout -k 10 400 bash tools/time_variants.sh "${K:-k_}" > $O/ktime.txt 2>&1 || { tail -20 $O/ktime.txt; exit 1; }
 cat $O/ktime.txt
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['matches']['value']);[print(k,v['avg_us'],v['launches']) for k,v in d['stages'].items()];print('C4',d['other_configs']['C4']['ms_per_step'])"

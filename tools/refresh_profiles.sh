@@ -20,9 +20,9 @@ bash tools/pmc.sh $O/pmc > $O/pmc.log 2>&1
 python3 tools/pmc_summary.py $O/pmc > $O/pmc_summary.txt
 mkdir -p profiles/$R && cp $O/pmc_summary.txt profiles/$R/pmc_summary.txt  # the bench line's roofline_valu reads it
 echo pmc-done
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench-done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py > $O/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full > $O/prof.log 2>&1
 echo prof-done
 grep '"metric"' $O/prof.log > $O/bench_profiled.json
 python3 tools/roofline_check.py $O/bench_profiled.json $O/prof/run_kernel_trace.csv > $O/roofline_check.json

@@ -3,10 +3,10 @@
 its launches in the bench's serialized pass (one whole-batch launch per step, per level for
 k_blur_resize), timed with HIP events on the kernel's stream.  Here the same launches are located
 in the trace and their mean duration gives frac = bytes_per_launch / mean / peak, which must agree
-with the line's frac (within 10%).  The timed region's concurrent launches (chunk
-grids, other chunks' stages beside them) are reported beside it.
+with the line's frac (within 10%).  The concurrent launches (the timed steps run again
+after the serialized pass: chunk grids, other chunks' stages beside them) are reported beside it.
 Usage: python tools/roofline_check.py BENCH_JSON KERNEL_TRACE_CSV [chunks]
-BENCH_JSON: the line the profiled process itself printed."""
+BENCH_JSON: the line the profiled `bench.py --full` process itself printed."""
 import csv
 import json
 import re
@@ -51,8 +51,9 @@ def dur(r):
     return (end - int(r["Start_Timestamp"])) / 1e3
 n_ser = roof.get("launches") or 3  # serialized launches (3 steps x launches per step)
 per_step = max(1, n_ser // 3)
-# launch order: warm-up steps (chunk grids), the serialized pass (whole-batch grids, the kernel
-# alone on the GPU), then the timed region (chunk grids again)
+# launch order of `bench.py --full`: warm-up and timed steps (chunk grids), the serialized pass
+# (whole-batch grids, the kernel alone on the GPU), then the timed steps run again with HIP events
+# around the dominant kernel (chunk grids again): the line's `concurrent` launches
 first = {grid(r) for r in rows[:warmup * chunks * per_step]}
 i = 0
 while i < len(rows) and grid(rows[i]) in first:
