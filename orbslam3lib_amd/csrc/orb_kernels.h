@@ -1,4 +1,5 @@
-// orb_kernels.h -- launch-argument structs shared by orb_kernels.hip and orb_runtime.cpp.
+// orb_kernels.h -- launch-argument structs shared by the kernel files and the host runtime
+// (orb_geometry.h fills them, orb_runtime.cpp and orb_post.cpp bind the pointers and launch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -19,7 +20,7 @@ __device__ inline int xcd_remap(int orig, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
 }
 
-// Per-level geometry, computed on the host (orb_runtime.cpp) from the reference formulas.
+// Per-level geometry, computed on the host (orb_geometry.h plan_geometry) from the reference formulas.
 struct LevelGeom {
     int w, h, pitch;           // plane size; pitch in bytes (level 0: the input's row stride)
     long long img_stride;      // bytes between images for this level's plane
@@ -141,7 +142,7 @@ constexpr int kKnnSplitSlots = KNN_SPLIT;   // pairs x splits the partial buffer
 // ceil(out_cap / kKnnQueries) query blocks per pair
 constexpr int kKnnQueries = 256;
 // arrival counters of the fused split merge: one per (pair of the launch, query block); a split
-// launch has at most kKnnSplitSlots / 2 pairs (orb_runtime.cpp), sized for kKnnSplitSlots
+// launch has at most kKnnSplitSlots / 2 pairs (orb_post.cpp orbgpu_match_stereo_batch), sized for kKnnSplitSlots
 __host__ inline size_t knn2_counter_slots(int out_cap) {
     return (size_t)kKnnSplitSlots * (size_t)((out_cap + kKnnQueries - 1) / kKnnQueries);
 }
@@ -213,7 +214,7 @@ constexpr int kOdKpBlock = 8;  // keypoints per k_orient_desc pass (256 threads,
 // keypoints per k_orient_desc workgroup by default: 3 passes of kOdKpBlock.  Round 5, chunked
 // moments, single stream per 512 images: 1 pass 553 us, 2 passes 483, 3 passes 463, 4 passes 467;
 // headline at 3 vs 2 passes +0.2 to +2.3% (bench A/B, 3 rounds).  Contexts of a few images take 1
-// (orb_runtime.cpp set_geometry).
+// (orb_geometry.h plan_geometry).
 constexpr int kOdBlockKps = 3 * kOdKpBlock;
 
 constexpr int kOctLdsKeys = 16384;  // per-key node labels (u16) kept in LDS up to this many keys

@@ -1,11 +1,14 @@
 // host_harness.hip -- TEST INFRASTRUCTURE: runs the device algorithm headers of the product
-// (orb_octree.h, orb_fast_cell.h, orb_introsort.h, orb_math.h) on the host with SerialPolicy so
-// they can be checked against the CPU oracle without a GPU.  Not part of liborbgpu.so.
+// (orb_octree.h, orb_fast_cell.h, orb_introsort.h, orb_math.h) on the host with SerialPolicy, and
+// the runtime's geometry planner (orb_geometry.h), so they can be checked against the CPU oracle
+// without a GPU.  Not part of liborbgpu.so.
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../orbslam3lib_amd/csrc/orb_fast_cell.h"
+#include "../../orbslam3lib_amd/csrc/orb_geometry.h"
 #include "../../orbslam3lib_amd/csrc/orb_introsort.h"
 #include "../../orbslam3lib_amd/csrc/orb_math.h"
 #include "../../orbslam3lib_amd/csrc/orb_octree.h"
@@ -237,53 +240,120 @@ int harness_fast_strength_corner(const uint8_t* img, int stride, int x, int y) {
     return fast_strength_corner(img + (long long)y * stride + x, stride);
 }
 
-// ComputeKeyPointsOctTree cell loop geometry (same formulas as orb_runtime.cpp) + fast_cell_run.
+// The planner (orb_geometry.h plan_geometry) with the product's knobs, for Python: lv gets
+// kPlanLevelFields int64 per level, sc kPlanScalars int64, rtab up to rtab_cap int4 as 4 int32
+// each (*rtab_n = how many the plan has).  The two name lists give the order.  Returns the
+// planner's status; err receives its message.
+#define PLAN_LEVEL_FIELDS(X)                                                                          \
+    X(w) X(h) X(pitch) X(img_stride) X(bpitch) X(bimg_stride) X(nCols) X(nRows) X(wCell) X(hCell)     \
+    X(maxBX) X(maxBY) X(ncells) X(cell_cap) X(cell_first) X(cellkey_off) X(cellcnt_off) X(cand_cap)   \
+    X(N) X(W) X(H) X(kp_cap) X(kp_off) X(oct_cap) X(oct_off) X(patch) X(tiles_x) X(tiles_y)           \
+    X(tile_first) X(xtab_off) X(ytab_off) X(simd_end) X(area2) X(band_row_off) X(tile_quad_off)       \
+    X(od_blocks) X(od_first) X(tpitch)
+#define PLAN_ARG_SCALARS(X)                                                                           \
+    X(nlevels) X(out_cap) X(tail0) X(tail_lds) X(tail_buf1) X(tail_tab) X(tail_maxq) X(tail_maxrows)  \
+    X(tail_min) X(oct_lds_nodes) X(oct_lds_bytes) X(oct_nq_off) X(oct_split) X(oct_split_min_images)  \
+    X(oct2_threads) X(oct2_lds_nodes) X(oct2_lds_bytes) X(oct2_nq_off) X(oct2_lds_keys)               \
+    X(oct_may_retry) X(oct_force_retry) X(oct_pyr_max) X(total_cells) X(total_tiles)                  \
+    X(total_od_blocks) X(fast_tab_off) X(od_tab_off) X(fast_n48) X(fast_n64) X(fast_qcap)             \
+    X(cellkeys_img_stride) X(cellcnt_img_stride) X(octws_img_stride) X(lvlkp_img_stride)
+#define PLAN_NAME(f) #f ","
+const char* harness_plan_level_fields() {
+    return PLAN_LEVEL_FIELDS(PLAN_NAME) "scale_bits,pyr_off,blur_off,oct_total,oct_nodemem,oct_nodemem_need";
+}
+const char* harness_plan_scalars() {
+    return PLAN_ARG_SCALARS(PLAN_NAME) "pyr_img,blur_img,cellkeys_img,octws_img,cellcnt_img,lvlkp_img,plan_out_cap,"
+                                       "generic_pyr,rtab_n,kBrMaxRows,kBrMaxQuads,kTailLdsMax,kOctLdsNodes,kBlurTW,kBlurTH";
+}
+int harness_plan_geometry(int w, int h, int nlevels, float scale_factor, int nfeatures, int max_images,
+                          long long* lv, long long* sc, int32_t* rtab, int rtab_cap, int* rtab_n, char* err,
+                          int err_cap) {
+    const orbgpu_params prm{nfeatures, scale_factor, nlevels, 20, 7};
+    GeomPlan P;
+    std::string msg;
+    const int r = plan_geometry(build_tables(prm), prm, w, h, max_images, GeomKnobs{}, &P, &msg);
+    if (err && err_cap > 0) {
+        std::strncpy(err, msg.c_str(), err_cap - 1);
+        err[err_cap - 1] = 0;
+    }
+    if (r) return r;
+#define PLAN_PUT(f) *o++ = (long long)G.f;
+    long long* o = lv;
+    for (int l = 0; l < nlevels; ++l) {
+        const LevelGeom& G = P.A.lv[l];
+        PLAN_LEVEL_FIELDS(PLAN_PUT)
+        const OctLayout ol = oct_layout(G.cand_cap, G.oct_cap);
+        *o++ = __builtin_bit_cast(uint32_t, G.scale);
+        *o++ = P.pyr_off[l];
+        *o++ = P.blur_off[l];
+        *o++ = ol.total;
+        *o++ = ol.nodemem;
+        *o++ = (long long)oct_nodemem_bytes(G.oct_cap);
+    }
+    o = sc;
+    {
+        const BatchArgs& G = P.A;
+        PLAN_ARG_SCALARS(PLAN_PUT)
+    }
+    for (long long v : {P.pyr_img, P.blur_img, P.cellkeys_img, P.octws_img, (long long)P.cellcnt_img,
+                        (long long)P.lvlkp_img, (long long)P.out_cap, (long long)P.generic_pyr,
+                        (long long)P.rtab.size(), (long long)kBrMaxRows, (long long)kBrMaxQuads,
+                        (long long)kTailLdsMax, (long long)kOctLdsNodes, (long long)kBlurTW, (long long)kBlurTH})
+        *o++ = v;
+    *rtab_n = (int)P.rtab.size();
+    std::memcpy(rtab, P.rtab.data(), sizeof(int4) * std::min<size_t>(P.rtab.size(), (size_t)std::max(rtab_cap, 0)));
+    return 0;
+}
+
+// ComputeKeyPointsOctTree cell loop over one level: the cell grid and the per-cell records are the
+// planner's (a one-level plan of w x h, orb_geometry.h), the cells run through fast_cell_run.
 int harness_level_candidates(const uint8_t* lvl, int w, int h, int ini, int mn, uint32_t* out,
                              int cap) {
-    const int minB = 16, maxBX = w - 16, maxBY = h - 16;
-    const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
-    const int nCols = (int)(width / 35.f), nRows = (int)(height / 35.f);
-    const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
+    const orbgpu_params prm{0, 1.2f, 1, ini, mn};
+    GeomPlan P;
+    if (plan_geometry(build_tables(prm), prm, w, h, 1, GeomKnobs{}, &P, nullptr)) return -1;
+    const LevelGeom& G = P.A.lv[0];
     std::vector<uint32_t> T32(kCellMax * kCellMax / 4), M32(kCellMax * kCellMax / 4);
     uint8_t* T = reinterpret_cast<uint8_t*>(T32.data());
     uint8_t* M = reinterpret_cast<uint8_t*>(M32.data());
     std::vector<uint16_t> list(cell_list_cap<kCellMax>() + 1);
     std::vector<int32_t> wcnt(4);
     std::vector<uint32_t> tmp(kCellMax * kCellMax);
-    int total = 0, cnt = 0;
+    int total = 0;
     SerialPolicy p;
-    for (int i = 0; i < nRows; ++i)
-        for (int j = 0; j < nCols; ++j) {
-            CellGeom g;
-            g.iniY = minB + i * hCell;
-            g.iniX = minB + j * wCell;
-            g.minBorder = minB;
-            if (g.iniY >= maxBY - 3 || g.iniX >= maxBX - 6) continue;
-            g.rows = std::min(g.iniY + hCell + 6, maxBY) - g.iniY;
-            g.cols = std::min(g.iniX + wCell + 6, maxBX) - g.iniX;
-            // alternate the two load paths (dword-aligned window / plain bytes) across cells
-            const bool dw = ((i + j) & 1) == 0 && (w & 3) == 0;
-            const int sh = dw ? (g.iniX & 3) : 0;
-            CellScratch cs{T, M, list.data(), wcnt.data()};
-            // the small tile whenever the cells fit it (as the runtime picks it), else the general one
-            const bool small = wCell + 9 <= kCellPitchSmall && hCell + 6 <= kCellPitchSmall;
-            const long long roi = (long long)g.iniY * w + g.iniX - sh;
-            const uint8_t* src = lvl + roi;
-            const long long size = (long long)w * h;
-            auto ld16 = [&](long long off) {  // bounds-checked like the device buffer load
-                uint8_t b[16];
-                for (int k = 0; k < 16; ++k) b[k] = roi + off + k < size ? src[off + k] : 0;
-                uint4 v;
-                std::memcpy(&v, b, 16);
-                return v;
-            };
-            const int m = small ? fast_cell_run<kCellPitchSmall>(p, src, w, sh, dw, g, ini, mn, cs, tmp.data(), ld16)
-                                : fast_cell_run<kCellMax>(p, src, w, sh, dw, g, ini, mn, cs, tmp.data(), ld16);
-            for (int k = 0; k < m; ++k) {
-                if (total < cap) out[total] = tmp[k];
-                ++total;
-            }
+    // the small tile whenever the cells fit it (as the runtime picks it), else the general one
+    const bool small = P.A.fast_n64 > 0;
+    for (int cell = 0; cell < G.ncells; ++cell) {
+        const int4 rec = P.rtab[P.A.fast_tab_off + 2 * cell], rec2 = P.rtab[P.A.fast_tab_off + 2 * cell + 1];
+        if (rec2.z) continue;  // skip
+        const int i = cell / G.nCols, j = cell % G.nCols;
+        CellGeom g;
+        g.iniX = rec.y;
+        g.iniY = rec.z;
+        g.minBorder = kMinBorder;
+        g.rows = rec.w & 0xFFFF;
+        g.cols = rec.w >> 16;
+        // alternate the two load paths (dword-aligned window / plain bytes) across cells
+        const bool dw = ((i + j) & 1) == 0 && (w & 3) == 0;
+        const int sh = dw ? (g.iniX & 3) : 0;
+        CellScratch cs{T, M, list.data(), wcnt.data()};
+        const long long roi = (long long)g.iniY * w + g.iniX - sh;
+        const uint8_t* src = lvl + roi;
+        const long long size = (long long)w * h;
+        auto ld16 = [&](long long off) {  // bounds-checked like the device buffer load
+            uint8_t b[16];
+            for (int k = 0; k < 16; ++k) b[k] = roi + off + k < size ? src[off + k] : 0;
+            uint4 v;
+            std::memcpy(&v, b, 16);
+            return v;
+        };
+        const int m = small ? fast_cell_run<kCellPitchSmall>(p, src, w, sh, dw, g, ini, mn, cs, tmp.data(), ld16)
+                            : fast_cell_run<kCellMax>(p, src, w, sh, dw, g, ini, mn, cs, tmp.data(), ld16);
+        for (int k = 0; k < m; ++k) {
+            if (total < cap) out[total] = tmp[k];
+            ++total;
         }
+    }
     return total;
 }
 
