@@ -23,8 +23,11 @@ $(OBJDIR)/%.o: $(CSRC)/% $(HDRS)
 $(LIB): $(LIBOBJ)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(LIBOBJ)
 
+# the CPU oracle, then (where a reference checkout exists; a no-op elsewhere) the reference's own
+# extractor built against it: oracle/ref/README.md
 oracle:
 	$(MAKE) -s -C oracle
+	$(MAKE) -s -C oracle/ref
 
 # C++ facade (what an ORB-SLAM3 build compiles) + its GPU test program
 FACADE_TEST := tests/cpp/build/facade_test
@@ -48,5 +51,6 @@ $(IDL_TEST): tests/c/idl_test.c include/orbgpu.h $(LIB)
 clean:
 	rm -f $(LIB) $(LIBOBJ)
 	$(MAKE) -s -C oracle clean
+	$(MAKE) -s -C oracle/ref clean
 
 .PHONY: all oracle clean facade_test idl_test
