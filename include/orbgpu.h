@@ -281,6 +281,50 @@ int orbgpu_search_by_projection_stereo(orbgpu_ctx* ctx, int n_pairs, const orbgp
 int orbgpu_download_projection_matches(orbgpu_ctx* ctx, int frame, int32_t* match, int cap, int* n_kp,
                                        int* nmatches);
 
+/* ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) ----------------------
+ * Tracking::TrackWithMotionModel's frame-to-frame search (cpp/src/ORBmatcher.cc:1683-1838 with
+ * ComputeThreeMaxima :2061-2102; pinhole frames, Nleft == -1: monocular or rectified stereo).  Every
+ * valid last-frame point is transformed with the current pose, projected (Pinhole.cpp:40-41) and
+ * matched in a window of th * mvScaleFactors[octave] on the grid of orbgpu_undistort_grid_batch:
+ * levels >= octave when the camera moved forward (tlc.z > mb, not mono), <= octave backward,
+ * octave +-1 otherwise; best Hamming distance <= TH_HIGH = 100, no ratio test; then the rotation
+ * histogram (30 bins, factor 1/30 as the reference) and the three-maxima rule when
+ * check_orientation != 0.  All arithmetic is IEEE single, evaluated in the reference's order.
+ * Frames, kp_block, host arrays and the stream are as in orbgpu_search_by_projection_batch; mbf /
+ * mb are Frame::mbf / Frame::mb, K = {fx, fy, cx, cy}.
+ * Deviations (the reference reads out of range there): a point whose projection is not finite or
+ * whose octave is outside [0, nlevels) is skipped; an event whose bin is outside [0, 30) (angles
+ * outside [0, 360)) counts in nmatches but enters no bin.
+ * The two-camera branch (:1840-1914) and the relocalisation overload (:1923-2059) have no entry
+ * point. */
+typedef struct {
+    float pos[3];      /* pMP->GetWorldPos() */
+    float angle;       /* LastFrame.mvKeysUn[i].angle */
+    int32_t octave;    /* LastFrame.mvKeys[i].octave (nLastOctave) */
+    int32_t flags;     /* ORBGPU_LP_VALID: mvpMapPoints[i] && !mvbOutlier[i];
+                          ORBGPU_MP_HAS_OBS: pMP->Observations() > 0 */
+    uint8_t desc[32];  /* pMP->GetDescriptor() */
+} orbgpu_last_point;   /* 56 bytes */
+#define ORBGPU_LP_VALID 1
+
+typedef struct {
+    float Rcw[9], tcw[3];  /* CurrentFrame.GetPose(), row-major */
+    float Rlw[9], tlw[3];  /* LastFrame.GetPose() */
+} orbgpu_track_pose;
+
+/* pts: all frames' last-frame points, frame f's in [pt_offsets[f], pt_offsets[f + 1]); poses: one
+ * per frame.  orbgpu_download_track_matches: match[k] = index (within the frame's points) of the
+ * last-frame point that ends up in CurrentFrame.mvpMapPoints[k], -1 if none; *nmatches = the
+ * reference's return value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when
+ * check_orientation == 0). */
+int orbgpu_track_by_projection_batch(orbgpu_ctx* ctx, int n_frames, int image_step, int use_uright,
+                                     const orbgpu_last_point* pts, const int32_t* pt_offsets,
+                                     const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
+                                     const uint8_t* kp_block, int kp_stride, float th, int mono,
+                                     int check_orientation, void* stream);
+int orbgpu_download_track_matches(orbgpu_ctx* ctx, int frame, int32_t* match, int cap, int* n_kp,
+                                  int* nmatches, int32_t rot_hist[30]);
+
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,
  * ORBextractor.cc:131-143; DSP split orbslam_dsp.cpp:643-648): frame f's left half (columns

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 __all__ = ["ORBextractor", "ORBmatcher", "BFMatcher", "BatchExtractor", "KEYPOINT_DTYPE", "MAP_POINT_DTYPE",
-           "OrbGpuError", "load_library", "LIB_PATH"]
+           "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "OrbGpuError", "load_library", "LIB_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # ORBGPU_LIB names another build of the same library (measurement variants under tools/)
@@ -30,6 +30,13 @@ MAP_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<
                             ("depth", "<f4"), ("level", "<i4"), ("flags", "<i4"), ("desc", "u1", (32,)),
                             ("proj_yr", "<f4"), ("view_cos_r", "<f4"), ("level_r", "<i4")])
 MP_IN_VIEW, MP_BAD, MP_HAS_OBS, MP_IN_VIEW_R = 1, 2, 4, 8
+
+# orbgpu_last_point (56 B): what the motion-model SearchByProjection reads of a last-frame point;
+# orbgpu_track_pose (96 B): CurrentFrame.GetPose() and LastFrame.GetPose(), row-major
+LAST_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("octave", "<i4"), ("flags", "<i4"),
+                             ("desc", "u1", (32,))])
+TRACK_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,))])
+LP_VALID = 1  # ORBGPU_LP_VALID (MP_HAS_OBS is shared)
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -52,7 +59,7 @@ EXPORTED = [
     "orbgpu_reset_stage_times", "orbgpu_last_error", "orbgpu_abi_version",
     "orbgpu_fisheye_stereo_batch", "orbgpu_download_fisheye", "orbgpu_run_batch_match",
     "orbgpu_diagnostic_knobs", "orbgpu_ingest_images", "orbgpu_export_batch_bytes", "orbgpu_export_batch",
-    "orbgpu_get_device",
+    "orbgpu_get_device", "orbgpu_track_by_projection_batch", "orbgpu_download_track_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -636,21 +643,21 @@ class BatchExtractor:
         return tuple(a[:n.value] for a in r)
 
     @staticmethod
-    def _map_point_rows(map_points):
+    def _map_point_rows(map_points, dtype=MAP_POINT_DTYPE):
         """(points, offsets, n_frames) for the C ABI: map_points is either a list (one per frame)
-        of MAP_POINT_DTYPE arrays, concatenated here, or a tuple (points, offsets) already in the
-        ABI's form -- every frame's points in one MAP_POINT_DTYPE array and int32 offsets [n + 1] --
-        which is passed through without a host copy."""
+        of `dtype` arrays (MAP_POINT_DTYPE; LAST_POINT_DTYPE for track_by_projection), concatenated
+        here, or a tuple (points, offsets) already in the ABI's form -- every frame's points in one
+        array and int32 offsets [n + 1] -- which is passed through without a host copy."""
         if isinstance(map_points, tuple):
             mps, off = map_points
-            mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+            mps = np.ascontiguousarray(mps, dtype)
             off = np.ascontiguousarray(off, np.int32)
             if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(mps) or np.any(np.diff(off) < 0):
                 raise ValueError("map point offsets must start at 0, not decrease and end at len(points)")
             return mps, off, len(off) - 1
         nf = len(map_points)
-        mps = np.ascontiguousarray(np.concatenate([np.asarray(m, MAP_POINT_DTYPE) for m in map_points])
-                                   if nf else np.zeros(0, MAP_POINT_DTYPE))
+        mps = np.ascontiguousarray(np.concatenate([np.asarray(m, dtype) for m in map_points])
+                                   if nf else np.zeros(0, dtype))
         off = np.zeros(nf + 1, np.int32)
         off[1:] = np.cumsum([len(m) for m in map_points])
         return mps, off, nf
@@ -712,6 +719,38 @@ class BatchExtractor:
         _check(_lib.orbgpu_download_projection_matches(self.ctx.handle, frame, _p(m), cap, C.byref(n),
                                                        C.byref(nm)))
         return m[:n.value], nm.value
+
+    def track_by_projection(self, points, poses, K, mbf, mb, image_step=2, use_uright=True, kp_block=None,
+                            th=15.0, mono=False, check_orientation=True, stream=None):
+        """ORBmatcher(nnratio, check_orientation).SearchByProjection(CurrentFrame, LastFrame, th, mono)
+        (ORBmatcher.cc:1683-1838, Tracking::TrackWithMotionModel) for frames f = images f * image_step
+        after undistort_grid(); points: list (one per frame) of LAST_POINT_DTYPE arrays, or (points,
+        offsets) as for search_by_projection; poses: TRACK_POSE_DTYPE array, one row per frame;
+        K = (fx, fy, cx, cy); kp_block as for search_by_projection."""
+        pts, off, nf = self._map_point_rows(points, LAST_POINT_DTYPE)
+        ps = np.ascontiguousarray(poses, TRACK_POSE_DTYPE).reshape(-1)
+        if len(ps) != nf:
+            raise ValueError("one pose per frame")
+        Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
+        blk, stride = None, 0
+        if kp_block is not None:
+            stride = max(1, max(len(b) for b in kp_block))
+            blk = np.zeros((nf, stride), np.uint8)
+            for f, b in enumerate(kp_block):
+                blk[f, :len(b)] = b
+        _check(_lib.orbgpu_track_by_projection_batch(
+            self.ctx.handle, nf, int(image_step), int(use_uright), _p(pts) if len(pts) else None, _p(off), _p(ps),
+            _p(Kf), C.c_float(mbf), C.c_float(mb), _p(blk) if blk is not None else None, stride, C.c_float(th),
+            int(mono), int(check_orientation), C.c_void_p(stream) if stream else None))
+
+    def track_matches(self, frame, cap=65536):
+        """(match [n_kp] int32: last-frame point index or -1, nmatches, rot_hist [30] int32: the bin
+        sizes before the three-maxima rule) of frame `frame`."""
+        m = np.zeros(cap, np.int32)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_track_matches(self.ctx.handle, frame, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
+        return m[:n.value], nm.value, h
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

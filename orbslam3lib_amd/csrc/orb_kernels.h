@@ -357,6 +357,56 @@ struct SbpArgs {
 size_t sbp_resolve_lds_bytes(int out_cap, int two_cam);
 hipError_t launch_sbp(const SbpArgs& a, int nframes, int max_mps, hipStream_t st);
 
+// ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (orb_track.hip).
+struct LastPointIn {  // orbgpu_last_point (56 B)
+    float pos[3], angle;
+    int32_t octave, flags;
+    uint8_t desc[32];
+};
+constexpr int kLpValid = 1;  // kMpHasObs (4) is shared with the local-map search
+constexpr int kTrackForward = 1, kTrackBackward = 2;
+struct TrackFrame {  // per frame, from orbgpu_track_pose (host: the direction, :1727-1734)
+    float Rcw[9], tcw[3];
+    int32_t dir;  // kTrackForward / kTrackBackward / 0
+    int32_t pad[3];
+};
+struct TrackCand {  // k_track_candidates -> k_track_resolve
+    int32_t idx[4];   // 4 lowest (distance, window position)
+    int32_t dist[4];
+    int32_t n;        // candidates after the filters; -1: point skipped
+    int32_t flags;
+    int32_t octave;
+    float u, v, invz, angle;  // the projection (:1742-1751) and LastFrame.mvKeysUn[i].angle
+    int32_t pad;
+};
+constexpr int kRotBins = 30;  // HISTO_LENGTH
+struct TrackArgs {
+    const LastPointIn* pts;   // all frames' points, frame f = [pt_off[f], pt_off[f + 1])
+    const int32_t* pt_off;
+    const TrackFrame* frames; // [frame]
+    TrackCand* cand;          // [point]
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const float* xy_un;       // grid buffers (orbgpu_undistort_grid_batch)
+    const int32_t* cell_start;
+    const int32_t* cell_idx;
+    const uint8_t* desc;      // out_desc
+    const float* uright;      // [frame][out_cap] mvuRight or nullptr
+    const uint8_t* kp_block;  // [frame][out_cap] pre-call occupant with observations, or nullptr
+    int image_step;           // frame f = batch image f * image_step
+    float bounds[4], grid_inv[2];
+    float scale[kMaxLevels];
+    int nlevels;
+    float K[4], mbf, th;
+    int check_orientation;
+    int32_t* match;           // [frame][out_cap]
+    int32_t* nmatches;        // [frame]
+    int32_t* rot_hist;        // [frame][kRotBins] bin sizes before the three-maxima rule
+};
+size_t track_resolve_lds_bytes(int out_cap);
+hipError_t launch_track(const TrackArgs& a, int nframes, int max_pts, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

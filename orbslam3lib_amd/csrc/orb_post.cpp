@@ -665,6 +665,115 @@ int orbgpu_download_projection_matches(orbgpu_ctx* c, int frame, int32_t* match,
     return ORBGPU_OK;
 }
 
+// ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (orb_track.hip) --------
+int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step, int use_uright,
+                                     const orbgpu_last_point* pts, const int32_t* pt_offsets,
+                                     const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
+                                     const uint8_t* kp_block, int kp_stride, float th, int mono,
+                                     int check_orientation, void* stream) {
+    static_assert(sizeof(orbgpu_last_point) == sizeof(LastPointIn) && sizeof(orbgpu_last_point) == 56,
+                  "last point layout");
+    static_assert(sizeof(orbgpu_track_pose) == 96, "track pose layout");
+    if (!c || !pt_offsets || !poses || !K || n_frames < 1) return fail(ORBGPU_ERR_INVALID, "null argument");
+    if (image_step != 1 && image_step != 2) return fail(ORBGPU_ERR_INVALID, "image_step must be 1 or 2");
+    if ((n_frames - 1) * image_step + 1 > c->grid_images)
+        return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
+    if (use_uright && (image_step != 2 || n_frames > c->stereo_pairs))
+        return fail(ORBGPU_ERR_INVALID, "mvuRight needs image_step 2 and a stereo_matches_batch over the pairs");
+    if (track_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
+        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
+    if (kp_block && kp_stride < 1) return fail(ORBGPU_ERR_INVALID, "stride");
+    int max_pts = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        if (pt_offsets[f + 1] < pt_offsets[f] || pt_offsets[0] != 0) return fail(ORBGPU_ERR_INVALID, "pt_offsets");
+        max_pts = std::max(max_pts, pt_offsets[f + 1] - pt_offsets[f]);
+    }
+    const int total = pt_offsets[n_frames];
+    if (total > 0 && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
+    // the motion direction decides the window's level range (:1727-1734)
+    std::vector<TrackFrame> frames(n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        const orbgpu_track_pose& P = poses[f];
+        TrackFrame& T = frames[f];
+        std::memcpy(T.Rcw, P.Rcw, sizeof T.Rcw);
+        std::memcpy(T.tcw, P.tcw, sizeof T.tcw);
+        float twc[3];
+        for (int k = 0; k < 3; ++k) twc[k] = -((P.Rcw[k] * P.tcw[0] + P.Rcw[3 + k] * P.tcw[1]) + P.Rcw[6 + k] * P.tcw[2]);
+        const float tlc_z = ((P.Rlw[6] * twc[0] + P.Rlw[7] * twc[1]) + P.Rlw[8] * twc[2]) + P.tlw[2];
+        T.dir = mono ? 0 : tlc_z > mb ? kTrackForward : -tlc_z > mb ? kTrackBackward : 0;
+        T.pad[0] = T.pad[1] = T.pad[2] = 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t cap = (size_t)c->plan.out_cap;
+    if (c->trkpt.ensure((size_t)total * sizeof(LastPointIn) + 256) || c->trkoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
+        c->trkframe.ensure((size_t)n_frames * sizeof(TrackFrame) + 256) ||
+        c->trkcand.ensure((size_t)total * sizeof(TrackCand) + 256) || c->trkmatch.ensure((size_t)n_frames * cap * 4 + 256) ||
+        c->trknm.ensure((size_t)n_frames * (1 + kRotBins) * 4 + 256) ||
+        (kp_block && c->trkblk.ensure((size_t)n_frames * cap + 256)))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (motion-model search)");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int r = join_all(c, s);  // keypoints, grid and mvuRight come from the chunk streams
+    if (r) return r;
+    // host inputs are pageable: copy, then wait so the caller may reuse them on return
+    if (total) HIP_TRY(hipMemcpyAsync(c->trkpt.p, pts, (size_t)total * sizeof(LastPointIn), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->trkoff.p, pt_offsets, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->trkframe.p, frames.data(), (size_t)n_frames * sizeof(TrackFrame), hipMemcpyHostToDevice, s));
+    if (kp_block) {
+        HIP_TRY(hipMemsetAsync(c->trkblk.p, 0, (size_t)n_frames * cap, s));
+        HIP_TRY(hipMemcpy2DAsync(c->trkblk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), n_frames,
+                                 hipMemcpyHostToDevice, s));
+    }
+    TrackArgs a{};
+    a.pts = c->trkpt.as<LastPointIn>();
+    a.pt_off = c->trkoff.as<int32_t>();
+    a.frames = c->trkframe.as<TrackFrame>();
+    a.cand = c->trkcand.as<TrackCand>();
+    a.kps = c->outkps.p;
+    a.out_n = c->outn.as<int32_t>();
+    a.out_cap = c->plan.out_cap;
+    a.xy_un = c->gxy.as<float>();
+    a.cell_start = c->gstart.as<int32_t>();
+    a.cell_idx = c->gidx.as<int32_t>();
+    a.desc = c->outdesc.as<uint8_t>();
+    a.uright = use_uright ? c->stur.as<float>() : nullptr;
+    a.kp_block = kp_block ? c->trkblk.as<uint8_t>() : nullptr;
+    a.image_step = image_step;
+    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
+    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
+    for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
+    a.nlevels = c->prm.nlevels;
+    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
+    a.mbf = mbf;
+    a.th = th;
+    a.check_orientation = check_orientation != 0;
+    a.match = c->trkmatch.as<int32_t>();
+    a.nmatches = c->trknm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_frames;
+    r = timed(c, ST_SBP, s, [&] { return launch_track(a, n_frames, max_pts, s); });
+    if (r) return r;
+    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
+    c->trk_frames = n_frames;
+    c->trk_step = image_step;
+    c->need_fork = true;
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_track_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp, int* nmatches,
+                                  int32_t rot_hist[30]) {
+    if (!c || frame < 0 || frame >= c->trk_frames) return fail(ORBGPU_ERR_INVALID, "bad frame");
+    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+    int32_t nk = 0, nm = 0;
+    D2H(&nk, c->outn.as<int32_t>() + (size_t)frame * c->trk_step, 4);
+    D2H(&nm, c->trknm.as<int32_t>() + frame, 4);
+    if (int e = count_status(nk)) return e;
+    if (n_kp) *n_kp = nk;
+    if (nmatches) *nmatches = nm;
+    if (rot_hist) D2H(rot_hist, c->trknm.as<int32_t>() + c->trk_frames + (size_t)frame * kRotBins, 4 * kRotBins);
+    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
+    if (match && nk) D2H(match, c->trkmatch.as<int32_t>() + (size_t)frame * c->plan.out_cap, 4 * (size_t)nk);
+    return ORBGPU_OK;
+}
+
 int orbgpu_image_bounds(int cols, int rows, const float K[4], const float* dist, int ndist, float bounds[4]) {
     if (!K || !bounds || (ndist > 0 && !dist) || ndist < 0) return fail(ORBGPU_ERR_INVALID, "null argument");
     image_bounds_host(cols, rows, K, dist, ndist, bounds);

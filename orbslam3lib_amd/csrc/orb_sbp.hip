@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "orb_kernels.h"
+#include "orb_window.h"
 
 namespace orbgpu {
 namespace {
@@ -61,26 +62,6 @@ __device__ inline void top_insert(Top4& t, int idx, int dist, int lvl) {
     }
 }
 
-struct FrameView {
-    const float* xy;       // keypoint positions [out_cap][2] (mvKeysUn, or mvKeys / mvKeysRight)
-    const uint8_t* kp;     // out_kps rows (octave at +20)
-    const int32_t* cs;     // cell_start [3073]
-    const int32_t* ci;     // cell_idx
-    const uint8_t* desc;   // [out_cap][32]
-    const float* uright;   // mvuRight or nullptr
-};
-
-__device__ inline int octave_of(const FrameView& F, int k) {
-    return *reinterpret_cast<const int32_t*>(F.kp + (long long)k * 28 + 20);
-}
-
-__device__ inline int hamming32(const uint32_t q[8], const uint8_t* d) {
-    const uint4 a = *reinterpret_cast<const uint4*>(d);
-    const uint4 b = *reinterpret_cast<const uint4*>(d + 16);
-    return __popc(q[0] ^ a.x) + __popc(q[1] ^ a.y) + __popc(q[2] ^ a.z) + __popc(q[3] ^ a.w) +
-           __popc(q[4] ^ b.x) + __popc(q[5] ^ b.y) + __popc(q[6] ^ b.z) + __popc(q[7] ^ b.w);
-}
-
 // Map-point prologue shared by both windows (:50-61).
 __device__ inline bool mp_live(const SbpArgs& a, const MapPointIn& mp) {
     const int views = a.two_cam ? (kMpInView | kMpInViewR) : kMpInView;
@@ -109,58 +90,9 @@ __device__ inline bool mp_window_r(const SbpArgs& a, const MapPointIn& mp, float
     return true;
 }
 
-// GetFeaturesInArea (Frame.cc:673-735) + the per-candidate filters and distances of
-// :86-118 / :164-187, calling emit(idx, dist, octave) for each surviving candidate in window order.
-template <class Blocked, class Emit>
-__device__ inline void walk_window(const SbpArgs& a, const FrameView& F, float x, float y, int level, float rs,
-                                   float proj_xr, const uint32_t q[8], Blocked blocked, Emit emit) {
-    const int minX = max(0, (int)floorf((x - a.bounds[0] - rs) * a.grid_inv[0]));
-    if (minX >= kGridCols) return;
-    const int maxX = min(kGridCols - 1, (int)ceilf((x - a.bounds[0] + rs) * a.grid_inv[0]));
-    if (maxX < 0) return;
-    const int minY = max(0, (int)floorf((y - a.bounds[2] - rs) * a.grid_inv[1]));
-    if (minY >= kGridRows) return;
-    const int maxY = min(kGridRows - 1, (int)ceilf((y - a.bounds[2] + rs) * a.grid_inv[1]));
-    if (maxY < 0) return;
-    const int minLevel = level - 1, maxLevel = level;
-    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-    for (int ix = minX; ix <= maxX; ++ix) {
-        const int j1 = F.cs[ix * kGridRows + maxY + 1];
-        for (int j = F.cs[ix * kGridRows + minY]; j < j1; ++j) {  // cells iy = minY..maxY are adjacent
-            const int k = F.ci[j];
-            const int oct = octave_of(F, k);
-            if (checkLevels) {
-                if (oct < minLevel) continue;
-                if (maxLevel >= 0 && oct > maxLevel) continue;
-            }
-            const float2 p = *reinterpret_cast<const float2*>(F.xy + 2LL * k);
-            if (!(fabsf(p.x - x) < rs && fabsf(p.y - y) < rs)) continue;
-            if (blocked(k)) continue;
-            if (F.uright) {
-                const float ur = F.uright[k];
-                if (ur > 0 && fabsf(proj_xr - ur) > rs) continue;
-            }
-            emit(k, hamming32(q, F.desc + 32LL * k), oct);
-        }
-    }
-}
-
 __device__ inline FrameView frame_view(const SbpArgs& a, int f, int eye) {
-    const int img = (a.img0 + f) * a.image_step + eye;
-    FrameView F;
-    F.xy = a.xy_un + 2LL * img * a.out_cap;
-    F.kp = static_cast<const uint8_t*>(a.kps) + 28LL * img * a.out_cap;
-    F.cs = a.cell_start + (long long)img * (kGridCols * kGridRows + 1);
-    F.ci = a.cell_idx + (long long)img * a.out_cap;
-    F.desc = a.desc + 32LL * img * a.out_cap;
-    F.uright = a.uright && !a.two_cam ? a.uright + (long long)(a.img0 + f) * a.out_cap : nullptr;
-    return F;
-}
-
-__device__ inline void load_desc(const MapPointIn& mp, uint32_t q[8]) {
-    for (int w = 0; w < 8; ++w)
-        q[w] = (uint32_t)mp.desc[4 * w] | ((uint32_t)mp.desc[4 * w + 1] << 8) |
-               ((uint32_t)mp.desc[4 * w + 2] << 16) | ((uint32_t)mp.desc[4 * w + 3] << 24);
+    return frame_view_of(a, (a.img0 + f) * a.image_step + eye,
+                         a.uright && !a.two_cam ? a.uright + (long long)(a.img0 + f) * a.out_cap : nullptr);
 }
 
 __device__ inline void top_store(const Top4& t, int32_t idx[kTop], int32_t key[kTop]) {
@@ -186,13 +118,13 @@ __global__ __launch_bounds__(256) void k_sbp_candidates(SbpArgs a) {
     const uint8_t* blk = a.kp_block ? a.kp_block + (long long)(a.img0 + f) * ncomb : nullptr;
     const int nl = a.out_n[(a.img0 + f) * a.image_step];
     uint32_t q[8];
-    load_desc(mp, q);
+    load_desc(mp.desc, q);
     float rs;
     if (mp_window(a, mp, &rs)) {
         const FrameView F = frame_view(a, f, 0);
         Top4 t;
         top_init(t);
-        walk_window(a, F, mp.proj_x, mp.proj_y, mp.level, rs, mp.proj_xr, q,
+        walk_window(a, F, mp.proj_x, mp.proj_y, mp.level - 1, mp.level, rs, mp.proj_xr, q,
                     [&](int k) { return blk && blk[k]; }, [&](int k, int d, int o) { top_insert(t, k, d, o); });
         out.n = t.n;
         top_store(t, out.idx, out.key);
@@ -201,7 +133,7 @@ __global__ __launch_bounds__(256) void k_sbp_candidates(SbpArgs a) {
         const FrameView F = frame_view(a, f, 1);
         Top4 t;
         top_init(t);
-        walk_window(a, F, mp.proj_xr, mp.proj_yr, mp.level_r, rs, 0.f, q,
+        walk_window(a, F, mp.proj_xr, mp.proj_yr, mp.level_r - 1, mp.level_r, rs, 0.f, q,
                     [&](int k) { return blk && blk[nl + k]; }, [&](int k, int d, int o) { top_insert(t, k, d, o); });
         out.nR = t.n;
         top_store(t, out.idxR, out.keyR);
@@ -318,9 +250,9 @@ __global__ __launch_bounds__(64) void k_sbp_resolve(SbpArgs a) {
                             float rs;
                             mp_window(a, mp, &rs);
                             uint32_t q[8];
-                            load_desc(mp, q);
+                            load_desc(mp.desc, q);
                             bi = -1, bd = 256, bl = -1, sd = 256, sl = -1;
-                            walk_window(a, FL, mp.proj_x, mp.proj_y, mp.level, rs, mp.proj_xr, q, is_taken,
+                            walk_window(a, FL, mp.proj_x, mp.proj_y, mp.level - 1, mp.level, rs, mp.proj_xr, q, is_taken,
                                         [&](int k, int d, int o) {
                                             if (d < bd) {
                                                 sd = bd, sl = bl;
@@ -358,9 +290,9 @@ __global__ __launch_bounds__(64) void k_sbp_resolve(SbpArgs a) {
                             float rs;
                             mp_window_r(a, mp, &rs);
                             uint32_t q[8];
-                            load_desc(mp, q);
+                            load_desc(mp.desc, q);
                             bi = -1, bd = 256, bl = -1, sd = 256, sl = -1;
-                            walk_window(a, FR, mp.proj_xr, mp.proj_yr, mp.level_r, rs, 0.f, q, takenR,
+                            walk_window(a, FR, mp.proj_xr, mp.proj_yr, mp.level_r - 1, mp.level_r, rs, 0.f, q, takenR,
                                         [&](int k, int d, int o) {
                                             if (d < bd) {
                                                 sd = bd, sl = bl;

@@ -1,0 +1,143 @@
+// orb_window.h -- Frame::GetFeaturesInArea (Frame.cc:673-739) over a frame whose keypoints,
+// descriptors, grid and mvuRight live in HBM, shared by the two projection searches
+// (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "orb_kernels.h"
+
+namespace orbgpu {
+
+struct FrameView {
+    const float* xy;       // keypoint positions [out_cap][2] (mvKeysUn, or mvKeys / mvKeysRight)
+    const uint8_t* kp;     // out_kps rows (angle at +12, octave at +20)
+    const int32_t* cs;     // cell_start [3073]
+    const int32_t* ci;     // cell_idx
+    const uint8_t* desc;   // [out_cap][32]
+    const float* uright;   // mvuRight or nullptr
+};
+
+__device__ inline int octave_of(const FrameView& F, int k) {
+    return *reinterpret_cast<const int32_t*>(F.kp + (long long)k * 28 + 20);
+}
+
+__device__ inline float angle_of(const FrameView& F, int k) {
+    return *reinterpret_cast<const float*>(F.kp + (long long)k * 28 + 12);
+}
+
+__device__ inline int hamming32(const uint32_t q[8], const uint8_t* d) {
+    const uint4 a = *reinterpret_cast<const uint4*>(d);
+    const uint4 b = *reinterpret_cast<const uint4*>(d + 16);
+    return __popc(q[0] ^ a.x) + __popc(q[1] ^ a.y) + __popc(q[2] ^ a.z) + __popc(q[3] ^ a.w) +
+           __popc(q[4] ^ b.x) + __popc(q[5] ^ b.y) + __popc(q[6] ^ b.z) + __popc(q[7] ^ b.w);
+}
+
+__device__ inline void load_desc(const uint8_t desc[32], uint32_t q[8]) {
+    for (int w = 0; w < 8; ++w)
+        q[w] = (uint32_t)desc[4 * w] | ((uint32_t)desc[4 * w + 1] << 8) | ((uint32_t)desc[4 * w + 2] << 16) |
+               ((uint32_t)desc[4 * w + 3] << 24);
+}
+
+// The cells GetFeaturesInArea(x, y, rs) visits (Frame.cc:680-694); false: none.  a: the caller's
+// argument struct (bounds[4] = {mnMinX, mnMaxX, mnMinY, mnMaxY}, grid_inv[2]).
+struct CellRange {
+    int minX, maxX, minY, maxY;
+};
+template <class Args>
+__device__ inline bool window_cells(const Args& a, float x, float y, float rs, CellRange* r) {
+    r->minX = max(0, (int)floorf((x - a.bounds[0] - rs) * a.grid_inv[0]));
+    if (r->minX >= kGridCols) return false;
+    r->maxX = min(kGridCols - 1, (int)ceilf((x - a.bounds[0] + rs) * a.grid_inv[0]));
+    if (r->maxX < 0) return false;
+    r->minY = max(0, (int)floorf((y - a.bounds[2] - rs) * a.grid_inv[1]));
+    if (r->minY >= kGridRows) return false;
+    r->maxY = min(kGridRows - 1, (int)ceilf((y - a.bounds[2] + rs) * a.grid_inv[1]));
+    return r->maxY >= 0;
+}
+
+// The level and distance tests of GetFeaturesInArea (:705-722) and the callers' per-candidate
+// filters (ORBmatcher.cc:86-95 / :164-170 / :1790-1799) on keypoint k; *oct: its octave.
+// proj_xr: the projection the mvuRight test compares with (used when F.uright is set).
+template <class Blocked>
+__device__ inline bool window_accepts(const FrameView& F, int k, float x, float y, int minLevel, int maxLevel,
+                                      float rs, float proj_xr, Blocked blocked, int* oct) {
+    *oct = octave_of(F, k);
+    if ((minLevel > 0) || (maxLevel >= 0)) {  // bCheckLevels
+        if (*oct < minLevel) return false;
+        if (maxLevel >= 0 && *oct > maxLevel) return false;
+    }
+    const float2 p = *reinterpret_cast<const float2*>(F.xy + 2LL * k);
+    if (!(fabsf(p.x - x) < rs && fabsf(p.y - y) < rs)) return false;
+    if (blocked(k)) return false;
+    if (F.uright) {
+        const float ur = F.uright[k];
+        if (ur > 0 && fabsf(proj_xr - ur) > rs) return false;
+    }
+    return true;
+}
+
+// GetFeaturesInArea(x, y, rs, minLevel, maxLevel) + the filters and the distance, calling
+// emit(idx, dist, octave) for each surviving candidate in window order.
+template <class Args, class Blocked, class Emit>
+__device__ inline void walk_window(const Args& a, const FrameView& F, float x, float y, int minLevel, int maxLevel,
+                                   float rs, float proj_xr, const uint32_t q[8], Blocked blocked, Emit emit) {
+    CellRange r;
+    if (!window_cells(a, x, y, rs, &r)) return;
+    for (int ix = r.minX; ix <= r.maxX; ++ix) {
+        const int j1 = F.cs[ix * kGridRows + r.maxY + 1];
+        for (int j = F.cs[ix * kGridRows + r.minY]; j < j1; ++j) {  // cells iy = minY..maxY are adjacent
+            const int k = F.ci[j];
+            int oct;
+            if (!window_accepts(F, k, x, y, minLevel, maxLevel, rs, proj_xr, blocked, &oct)) continue;
+            emit(k, hamming32(q, F.desc + 32LL * k), oct);
+        }
+    }
+}
+
+// The same walk by a whole wave for one window (every lane passes the same arguments): lane l
+// takes entries l, l + 64, ... of each grid column's list.  Returns the first lowest distance in
+// window order to every lane (*best_idx = -1, distance 256 when nothing survives).
+template <class Args, class Blocked>
+__device__ inline int walk_window_wave(const Args& a, const FrameView& F, float x, float y, int minLevel,
+                                       int maxLevel, float rs, float proj_xr, const uint32_t q[8], Blocked blocked,
+                                       int lane, int* best_idx) {
+    uint32_t key = 0xFFFFFFFFu;  // distance << 16 | window position
+    int idx = -1;
+    CellRange r;
+    if (window_cells(a, x, y, rs, &r)) {
+        int base = 0;
+        for (int ix = r.minX; ix <= r.maxX; ++ix) {
+            const int j0 = F.cs[ix * kGridRows + r.minY], j1 = F.cs[ix * kGridRows + r.maxY + 1];
+            for (int j = j0 + lane; j < j1; j += 64) {
+                const int k = F.ci[j];
+                int oct;
+                if (!window_accepts(F, k, x, y, minLevel, maxLevel, rs, proj_xr, blocked, &oct)) continue;
+                const uint32_t kk = ((uint32_t)hamming32(q, F.desc + 32LL * k) << 16) | (uint32_t)(base + j - j0);
+                if (kk < key) key = kk, idx = k;
+            }
+            base += j1 - j0;
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t ok = __shfl_xor(key, o);
+        const int oi = __shfl_xor(idx, o);
+        if (ok < key) key = ok, idx = oi;
+    }
+    *best_idx = idx;
+    return idx >= 0 ? (int)(key >> 16) : 256;
+}
+
+// The frame's buffers: a.xy_un / kps / cell_start / cell_idx / desc over batch image img.
+template <class Args>
+__device__ inline FrameView frame_view_of(const Args& a, int img, const float* uright) {
+    FrameView F;
+    F.xy = a.xy_un + 2LL * img * a.out_cap;
+    F.kp = static_cast<const uint8_t*>(a.kps) + 28LL * img * a.out_cap;
+    F.cs = a.cell_start + (long long)img * (kGridCols * kGridRows + 1);
+    F.ci = a.cell_idx + (long long)img * a.out_cap;
+    F.desc = a.desc + 32LL * img * a.out_cap;
+    F.uright = uright;
+    return F;
+}
+
+}  // namespace orbgpu

@@ -184,3 +184,76 @@ def stereo_partners(descL, descR, seed=0, frac=0.6):
             l2r[i], r2l[j] = j, i
             free[j] = False
     return l2r, r2l
+
+
+def last_frame_points(xy_un, kps, desc, K, pose, uright=None, n=1000, seed=0, mbf=None, th=15.0,
+                      bounds=(0.0, 640.0, 0.0, 480.0), pool=None, obs_fraction=0.7, nlevels=8, scale_factor=1.2):
+    """Synthetic last-frame points for the motion-model SearchByProjection (a LAST_POINT_DTYPE
+    array): the current keypoints (xy_un, kps: KEYPOINT_DTYPE, desc) unprojected at random depths
+    through the inverse of pose = (Rcw 3x3, tcw 3) -- with uright and mbf the depth is
+    mbf / (u - uright) where a stereo match exists -- with sub-radius position noise, a few flipped
+    descriptor bits, the keypoint's octave +-1 and its angle plus a common offset and small noise.
+    Several points aim at each of `pool` keypoints (default n // 2).  Mixed in by fixed fractions:
+    invalid points (5%), points without observations (1 - obs_fraction), random angles (10%),
+    points behind the camera (3%), projections outside the bounds (4%, every side), octaves outside
+    [0, nlevels) (1%), non-finite positions (0.5%) and, with stereo, depths that disagree with
+    mvuRight (5%)."""
+    from . import LAST_POINT_DTYPE, LP_VALID, MP_HAS_OBS
+    rng = np.random.default_rng(seed)
+    xy_un = np.asarray(xy_un, np.float64).reshape(-1, 2)
+    octave = np.asarray(kps["octave"], np.int64)
+    kangle = np.asarray(kps["angle"], np.float64)
+    desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    nk = len(octave)
+    out = np.zeros(n, LAST_POINT_DTYPE)
+    if nk == 0 or n == 0:
+        return out
+    fx, fy, cx, cy = (float(v) for v in K)
+    Rcw = np.asarray(pose[0], np.float64).reshape(3, 3)
+    tcw = np.asarray(pose[1], np.float64).reshape(3)
+    scale = scale_factor ** np.arange(nlevels, dtype=np.float64)
+    npool = max(1, min(nk, n // 2 if pool is None else int(pool)))
+    k = rng.choice(nk, size=npool, replace=False)[rng.integers(0, npool, n)]
+    oct_l = np.clip(octave[k] + rng.choice([-1, 0, 0, 0, 1], n), 0, nlevels - 1)
+    radius = th * scale[oct_l]
+    uv = xy_un[k] + np.clip(rng.normal(0.0, 0.2, (n, 2)), -0.8, 0.8) * radius[:, None]
+    z = rng.uniform(1.0, 20.0, n)
+    if uright is not None and mbf is not None:
+        disp = xy_un[k, 0] - np.asarray(uright, np.float64)[k]
+        has = (np.asarray(uright, np.float64)[k] > 0) & (disp > 0.1)
+        z = np.where(has, mbf / np.where(has, disp, 1.0), z)
+        wrong = has & (rng.random(n) < 0.05)  # a disparity off by four radii
+        z = np.where(wrong, mbf / (np.where(has, disp, 1.0) + 4.0 * radius), z)
+    behind = rng.random(n) < 0.03
+    z = np.where(behind, -z, z)
+    outside = np.flatnonzero(rng.random(n) < 0.04)
+    far = rng.uniform(50.0, 300.0, len(outside))
+    for j, (i, d) in enumerate(zip(outside, far)):  # every side in turn
+        side = j % 4
+        if side == 0:
+            uv[i, 0] = bounds[0] - d
+        elif side == 1:
+            uv[i, 0] = bounds[1] + d
+        elif side == 2:
+            uv[i, 1] = bounds[2] - d
+        else:
+            uv[i, 1] = bounds[3] + d
+    pc = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    pw = (pc - tcw) @ Rcw  # Rcw^T (pc - tcw)
+    pw[rng.random(n) < 0.005] = np.nan
+    out["pos"] = pw.astype(np.float32)
+    oct_l = np.where(rng.random(n) < 0.01, rng.choice([-1, nlevels], n), oct_l)
+    out["octave"] = oct_l
+    ang = np.mod(kangle[k] + 20.0 + rng.normal(0.0, 3.0, n), 360.0)
+    ang = np.where(rng.random(n) < 0.10, rng.uniform(0.0, 360.0, n), ang)
+    out["angle"] = ang.astype(np.float32)
+    out["flags"] = np.where(rng.random(n) < 0.95, LP_VALID, 0) | np.where(rng.random(n) < obs_fraction, MP_HAS_OBS, 0)
+    d = desc[k].copy()
+    nflip = rng.choice([0, 2, 5, 10, 20, 35], n)
+    for i in range(n):
+        if nflip[i]:
+            b = np.unpackbits(d[i])
+            b[rng.choice(256, nflip[i], replace=False)] ^= 1
+            d[i] = np.packbits(b)
+    out["desc"] = d
+    return out
