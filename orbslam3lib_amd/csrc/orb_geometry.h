@@ -115,6 +115,7 @@ struct GeomKnobs {
     int oct_split = -1;                        // ORBGPU_OCT_SPLIT: forced split level (-1: policy)
     bool oct_generic = false;                  // ORBGPU_OCT_GENERIC: every level through k_octree_retry
     int oct_pyr_max = kOctPyrMaxD;             // ORBGPU_OCT_PYR: cap of the count pyramid's depth
+    bool oct_rounds = false;                   // ORBGPU_OCT_ROUNDS=1: phase 1 round by round with the pyramid too
     int fast_min_tier = 0;                     // ORBGPU_FAST_PITCH: 64 -> 1, 80 -> 2 (force the larger tiles)
 };
 
@@ -350,6 +351,7 @@ inline void octree_lds(const GeomKnobs& K, GeomPlan& P) {
     A.oct_force_retry = K.oct_generic ? 1 : 0;  // diagnostics / tests
     // ORBGPU_OCT_PYR=<d>: cap the count pyramid's depth (0: the label-pass formulation only)
     A.oct_pyr_max = K.oct_pyr_max;
+    A.oct_rounds = K.oct_rounds ? 1 : 0;  // A/B and tests: the round-by-round phase 1 (orb_octree.h)
     if (A.oct_force_retry) A.oct_may_retry = 1;
 }
 

@@ -105,6 +105,7 @@ struct BatchArgs {
     int oct_may_retry;               // some level can exceed the LDS instantiation of k_octree
     int oct_force_retry;             // diagnostics: every level through the generic instantiation
     int oct_pyr_max;                 // deepest count pyramid of k_octree (0: label passes only)
+    int oct_rounds;                  // diagnostics: phase 1 round by round with the pyramid too
     // k_pyr_tail: levels [tail0, nlevels) and the blurs of [tail0 - 1, nlevels) in one launch
     // (tail0 = nlevels + 1: no tail, k_blur_resize for every level and k_blur for the last)
     int tail0;

@@ -972,6 +972,7 @@ __device__ __attribute__((always_inline)) inline void octree_level(const BatchAr
         w.cell_cap = G.cell_cap;
         w.pyr = (asp<kLdsAS, uint32_t>)(nodemem_lds + pyr_off);
         w.pyrD = pyrD;
+        w.rounds = a.oct_rounds;
         w.xcode = (asp<kLdsAS, uint16_t>)xtbl;
         w.ycode = (asp<kLdsAS, uint16_t>)(xtbl + G.W + 1);
         r = octree_distribute(p, w, (asp<kLdsAS, OctShared>)&sh, G.W, G.H, G.N);
@@ -998,6 +999,7 @@ __device__ __attribute__((always_inline)) inline void octree_level(const BatchAr
         w.cell_cap = G.cell_cap;
         w.pyr = (asp<kLdsAS, uint32_t>)(nodemem_lds + pyr_off);
         w.pyrD = pyrD;
+        w.rounds = a.oct_rounds;
         w.xcode = (asp<kLdsAS, uint16_t>)xtbl;
         w.ycode = (asp<kLdsAS, uint16_t>)(xtbl + G.W + 1);
         r = octree_distribute(p, w, (asp<kLdsAS, OctShared>)&sh, G.W, G.H, G.N);

@@ -141,6 +141,9 @@ struct OctWST {
     int pyrD;
     asp<LAS, uint16_t> xcode;  // [W + 1] oct_xcode of every column (pyrD > 0)
     asp<LAS, uint16_t> ycode;  // [H + 1] oct_ycode of every row
+    // phase 1 with the pyramid: 0 builds its node list directly from the counts (the product),
+    // 1 walks it round by round as the label passes do (A/B and tests)
+    int rounds = 0;
 };
 
 constexpr int kOctUnroll = 8;         // keys per thread per batch in the key passes
@@ -150,6 +153,8 @@ constexpr int kOctUnroll = 8;         // keys per thread per batch in the key pa
 
 struct OctShared {
     int size, prev_size, nexp, ndiv, phase, done, nchild, nundiv, status, jstop, deep;
+    // direct phase 1: the existing nodes E_d (lower half) and one-key nodes S_d (upper half) of depth d
+    unsigned long long tot[kOctPyrMaxD + 1];
 };
 
 __host__ __device__ inline int oct_half(int a, int b) { return (b - a + 1) >> 1; }  // ceil((b-a)/2.f)
@@ -201,6 +206,45 @@ __host__ __device__ inline OctNode oct_child(OctNode nd, int q, int cnt) {
     return c;
 }
 
+// ---- direct phase 1 -----------------------------------------------------------------------
+// Phase 1 (:612-691) divides every node with more than one key in every round, so its list after
+// r rounds is a function of the count pyramid alone:
+//   * a node of depth d exists iff its count is >= 1 and its parent's is >= 2 (counts grow towards
+//     the root, so the parent's test covers every ancestor);
+//   * the list is O_r ++ F_{r-1} ++ ... ++ F_0: O_d the existing nodes of depth d, F_d those of
+//     them with one key (frozen in round d + 1, kept in their order behind every later child);
+//   * O_d ascends in the key k_d of the node's initial index i and quadrants q_1..q_d:
+//     k_0 = i, k_{d+1} = 4 (nIni 4^d - 1 - k_d) + (3 - q_{d+1}) -- push_front reverses the order
+//     of the parents once per round and puts n4 first;
+//   * the next round's candidates (vSizeAndPointerToNode: the final phase's sort input) are the
+//     nodes of O_r with more than one key in (division order, n1..n4) = descending k_r.
+// With E_d = |O_d|, S_d = |F_d| the list size after r rounds is E_r + sum_{d<r} S_d, which is
+// all the stop rule of :687-691 reads.
+//
+// Path index of the depth-d node at position k of the key order: k_d complements the base-4
+// digit of every second depth (from the last one) and, at odd depths, the initial index.
+__host__ __device__ inline uint32_t oct_key_path(int d, uint32_t k, int nIni) {
+    const uint32_t top = k >> (2 * d);
+    const uint32_t i = (d & 1) ? (uint32_t)nIni - 1u - top : top;
+    return (i << (2 * d)) | ((k ^ 0x33333333u) & ((1u << (2 * d)) - 1u));
+}
+// The initial node i (:561-575) and the node of a path index at depth d below it.
+__host__ __device__ inline OctNode oct_init(int i, float hX, int H, int cnt) {
+    OctNode nd;
+    nd.x0 = (uint16_t)(int)(hX * (float)i);
+    nd.x1 = (uint16_t)(int)(hX * (float)(i + 1));
+    nd.y0 = 0;
+    nd.y1 = (uint16_t)H;
+    nd.cnt = cnt;
+    nd.path = oct_path_code(0, (uint32_t)i);
+    return nd;
+}
+__host__ __device__ inline OctNode oct_node_of_path(int d, uint32_t idx, float hX, int H) {
+    OctNode nd = oct_init((int)(idx >> (2 * d)), hX, H, 0);
+    for (int s = d - 1; s >= 0; --s) nd = oct_child(nd, (int)((idx >> (2 * s)) & 3u), 0);
+    return nd;
+}
+
 // Runs DistributeOctTree for one level.  Coordinates are relative to (minBorderX, minBorderY);
 // W = maxBorderX-minBorderX, H = maxBorderY-minBorderY, N = mnFeaturesPerLevel[level].
 // Returns the number of output nodes (keys written to ws.out_keys in list order), or <0.
@@ -208,7 +252,10 @@ __host__ __device__ inline OctNode oct_child(OctNode nd, int q, int cnt) {
 // Work split: node-level phases (division order, sort, rebuild: a few hundred nodes) run on
 // p.node() -- wave 0 alone on the GPU, so their many scans need no workgroup barrier -- and
 // the key passes (relabel + child counts) run on every thread with the global key loads
-// software-pipelined; a phase-1 round costs two workgroup barriers.
+// software-pipelined; a phase-1 round costs two workgroup barriers.  With the count pyramid
+// phase 1 runs no rounds (unless ws.rounds asks for them): every thread tallies E_d and S_d while
+// it sums the pyramid's levels, walks the stop rule on them, and one scan over the key order
+// places every node of the list (direct phase 1, above); only final-phase rounds remain.
 // whole nodes as one 16-byte access (the node phases run on one wave: fewer LDS instructions)
 template <class NP>
 __host__ __device__ inline OctNode on_ld(NP a, int i) {
@@ -264,15 +311,13 @@ __host__ __device__ __attribute__((always_inline)) inline int octree_distribute(
     auto pcnt = ws.pyr;
     auto pbest = fast ? ws.pyr + pyr_base(D + 1, nIni) : ws.pyr;  // (no offset on a null pyr)
     const int bD = pyr_base(D, nIni);
-    if (fast) {
+    const bool direct = fast && !ws.rounds;
+    if (fast) {  // (one barrier with the path tables below: both only precede the histogram)
         for (int e = tid; e < (nIni << (2 * D)); e += NT) {
             pcnt[bD + e] = 0;
             pbest[bD + e] = 0;
         }
-        p.sync();
-#ifdef OCT_DIAG
-        mark(1);
-#endif
+        for (int e = tid; e <= kOctPyrMaxD; e += NT) sh->tot[e] = 0;
     }
     // every key pass: f(base, key[kOctUnroll]) handles keys k = base + u * NT + tid (u <
     // kOctUnroll; k >= n are padding) in stages across the batch so the LDS round trips of
@@ -417,31 +462,143 @@ __host__ __device__ __attribute__((always_inline)) inline int octree_distribute(
         p.sync();  // the cell offsets share memory with the node state written below
     }
     if (fast) {  // the levels above D: sums and maxima of the four children
+        // direct phase 1: the same pass tallies, per depth, the existing nodes (count >= 1 under
+        // a parent of >= 2) and those of them with one key -- a parent knows its four children
         for (int d = D - 1; d >= 0; --d) {
             const int b = pyr_base(d, nIni), b1 = pyr_base(d + 1, nIni);
-            for (int e = tid; e < (nIni << (2 * d)); e += NT) {
-                const int c = b1 + 4 * e;
-                pcnt[b + e] = pcnt[c] + pcnt[c + 1] + pcnt[c + 2] + pcnt[c + 3];
-                const uint32_t m0 = pbest[c] > pbest[c + 1] ? pbest[c] : pbest[c + 1];
-                const uint32_t m1 = pbest[c + 2] > pbest[c + 3] ? pbest[c + 2] : pbest[c + 3];
-                pbest[b + e] = m0 > m1 ? m0 : m1;
+            const int ne = nIni << (2 * d);
+            for (int base = 0; base < ne; base += NT) {  // (whole waves run every trip: the tallies ballot)
+                const int e = base + tid;
+                uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+                if (e < ne) {
+                    const int c = b1 + 4 * e;
+                    c0 = pcnt[c], c1 = pcnt[c + 1], c2 = pcnt[c + 2], c3 = pcnt[c + 3];
+                    // (all eight loads ahead of the stores: one LDS round trip)
+                    const uint32_t v0 = pbest[c], v1 = pbest[c + 1], v2 = pbest[c + 2], v3 = pbest[c + 3];
+                    const uint32_t m0 = v0 > v1 ? v0 : v1, m1 = v2 > v3 ? v2 : v3;
+                    pcnt[b + e] = c0 + c1 + c2 + c3;
+                    pbest[b + e] = m0 > m1 ? m0 : m1;
+                }
+                if (direct) {  // one compare and one scalar bit count per flag, one atomic per wave
+                    const uint32_t sum = c0 + c1 + c2 + c3;
+                    const bool dv = sum > 1;
+                    const int E = p.wave_count(dv && c0 > 0) + p.wave_count(dv && c1 > 0) +
+                                  p.wave_count(dv && c2 > 0) + p.wave_count(dv && c3 > 0);
+                    const int S = p.wave_count(dv && c0 == 1) + p.wave_count(dv && c1 == 1) +
+                                  p.wave_count(dv && c2 == 1) + p.wave_count(dv && c3 == 1);
+                    p.wave_add2(&sh->tot[d + 1], E, S);
+                    if (d == 0) p.wave_add2(&sh->tot[0], p.wave_count(sum > 0), p.wave_count(sum == 1));
+                }
             }
             p.sync();
         }
         mark(6);
     }
-    // ---- initial nodes (:561-603) ------------------------------------------------------
-    for (int i = tid; i < nIni; i += NT) {
-        OctNode nd;
-        nd.x0 = (uint16_t)(int)(hX * (float)i);
-        nd.x1 = (uint16_t)(int)(hX * (float)(i + 1));
-        nd.y0 = 0;
-        nd.y1 = (uint16_t)H;
-        nd.cnt = fast ? (int)pcnt[i] : 0;
-        nd.path = oct_path_code(0, (uint32_t)i);
-        on_st(cur, i, nd);
+    if (direct) {
+        // ---- phase 1 without rounds (direct phase 1, above) ---------------------------------
+        // the stop rule of :687-691 on the totals: R rounds, then the list is final, the final
+        // phase starts from it, or one of the two fallbacks applies
+        unsigned long long es = sh->tot[0];  // E_R | S_R << 32
+        int R = 0, size = (int)(uint32_t)es, prev = size, X = size - (int)(es >> 32), frozen = 0, status = 0;
+        bool final_phase = false;
+        while (X > 0) {  // (no candidate: the next round changes nothing and ends on size == prevSize)
+            frozen += (int)(es >> 32);
+            es = sh->tot[++R];
+            prev = size;
+            size = (int)(uint32_t)es + frozen;
+            X = (int)(uint32_t)es - (int)(es >> 32);
+            if (size > ws.cap - 4) {
+                status = -3;
+                break;
+            }
+            if (size >= N || size == prev) break;
+            final_phase = size + 3 * X > N;
+            // the next round would divide a node whose children lie below the pyramid
+            if (X > 0 && R >= D) {
+                status = kOctDeep;
+                break;
+            }
+            if (final_phase) break;
+        }
+        if (status) return status;  // (the same on every thread)
+        // the list in one pass over its order: the four key-order slots under each possible
+        // parent of depth R - 1 (O_R), then R - 2 .. 0 (F_{R-1} .. F_1), then the initial nodes
+        // (F_0; O_0 when no round ran)
+        const int nwork = R > 0 ? (nIni << (2 * (R - 1))) + pyr_base(R - 1, nIni) + nIni : nIni;
+        const int bR1 = pyr_base(R + 1, nIni);  // (read only ahead of the final phase: R < D)
+        int carry = 0, ccarry = 0;
+        for (int base = 0; base < nwork; base += NT) {
+            int t = base + tid, d = R;
+            const bool in = t < nwork;
+            if (in)
+                for (; d > 0; --d) {
+                    const int w = nIni << (2 * (d - 1));
+                    if (t < w) break;
+                    t -= w;
+                }
+            const bool head = d == R;  // O_R lists every existing node, F_d the one-key ones
+            uint32_t pp = 0;
+            int c[4] = {0, 0, 0, 0};
+            if (in && d == 0) {
+                c[0] = (int)pcnt[t];
+            } else if (in) {
+                // slots 4t .. 4t+3 of depth d's key order: the children n4 .. n1 of one parent
+                pp = oct_key_path(d - 1, (uint32_t)((nIni << (2 * (d - 1))) - 1 - t), nIni);
+                const bool divided = pcnt[pyr_base(d - 1, nIni) + (int)pp] > 1;  // (loaded beside the counts)
+                const int b = pyr_base(d, nIni) + 4 * (int)pp;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) c[q] = (int)pcnt[b + q];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) c[q] = divided ? c[q] : 0;
+            }
+            int nl = 0, nx = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                nl += head ? c[q] > 0 : c[q] == 1;
+                nx += final_phase && head && c[q] > 1;
+            }
+            int tl, tx;
+            const int2 ex = p.scan_small2(nl, nx, &tl, &tx);
+            if (nl) {
+                int pos = carry + ex.x, kc = ccarry + ex.y;
+                const OctNode par = d > 0 ? oct_node_of_path(d - 1, pp, hX, H) : oct_init(t, hX, H, c[0]);
+                if (d == 0) on_st(cur, pos, par);
+#pragma unroll
+                for (int q = 3; q >= 0; --q) {
+                    if (d == 0 || !(head ? c[q] > 0 : c[q] == 1)) continue;
+                    const OctNode ch = oct_child(par, q, c[q]);
+                    on_st(cur, pos, ch);
+                    if (final_phase && head && c[q] > 1) {
+                        // the final phase's candidates in the order of vSizeAndPointerToNode
+                        // (descending key order), with their child counts
+                        vsz[X - 1 - kc] = (uint16_t)pos;
+                        ++kc;
+                        const int b = bR1 + 4 * (int)oct_path_idx(ch.path);
+                        for (int qq = 0; qq < 4; ++qq) ccur[4 * pos + qq] = (int)pcnt[b + qq];
+                    }
+                    ++pos;
+                }
+            }
+            carry += tl;
+            ccarry += tx;
+        }
+        if (tid == 0) {
+            sh->size = size;
+            sh->prev_size = prev;
+            sh->nexp = X;
+            sh->phase = final_phase ? 2 : 1;
+            sh->done = final_phase ? 0 : 1;
+            sh->status = 0;
+            sh->deep = 0;
+        }
+        p.sync();
+        mark(4);
     }
-    p.sync();
+    // ---- initial nodes (:561-603) ------------------------------------------------------
+    if (!direct) {
+        for (int i = tid; i < nIni; i += NT) on_st(cur, i, oct_init(i, hX, H, fast ? (int)pcnt[i] : 0));
+        p.sync();
+    }
     if (!fast) {
         for_keys([&](int base, const uint32_t* key) __attribute__((always_inline)) {
 #pragma unroll
@@ -455,7 +612,7 @@ __host__ __device__ __attribute__((always_inline)) inline int octree_distribute(
         });
         p.sync();
     }
-    if (nw) {  // drop the empty initial nodes (:594-603)
+    if (nw && !direct) {  // drop the empty initial nodes (:594-603)
         auto np = p.node();
         const int ntid = np.tid(), NNT = np.nthreads();
         int carry = 0;
@@ -484,12 +641,12 @@ __host__ __device__ __attribute__((always_inline)) inline int octree_distribute(
             sh->deep = 0;
         }
     }
-    {
+    if (!direct) {
         auto t = cur;
         cur = nxt;
         nxt = t;
+        p.sync();
     }
-    p.sync();
     // relabel to the compacted list + count round 1 (every node with >1 key is a candidate)
     if (!fast) {
         for_keys([&](int base, const uint32_t* key) __attribute__((always_inline)) {
@@ -742,7 +899,8 @@ __host__ __device__ __attribute__((always_inline)) inline int octree_distribute(
                     sh->status = kOctDeep;
                     sh->done = 1;
                 }
-                if (ws.dbg) ws.dbg[7] += 1;
+                // rounds run; the phase-1 ones among them in the upper half
+                if (ws.dbg) ws.dbg[7] += phase == 1 ? (1ull << 32) + 1ull : 1ull;
             }
             mark(4);
         }

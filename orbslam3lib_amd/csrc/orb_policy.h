@@ -169,6 +169,41 @@ struct DevPolicy {
         *total = tot;
         return before + ex;
     }
+    // lanes of the calling wave with the flag set (one compare and one scalar bit count)
+    __device__ int wave_count(bool f) const { return __popcll(__ballot(f)); }
+    // *ptr += lo | hi << 32, once per calling wave (lo, hi: wave-uniform, e.g. sums of wave_count)
+    template <class T>
+    __device__ void wave_add2(T ptr, int lo, int hi) {
+        if ((threadIdx.x & 63) == 0 && (lo | hi))
+            __hip_atomic_fetch_add(ptr, (unsigned long long)(uint32_t)lo | ((unsigned long long)(uint32_t)hi << 32),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // block-wide exclusive scans of two values in [0, 7] with one pair of barriers (<= 8 waves)
+    __device__ int2 scan_small2(int a, int b, int* ta, int* tb) {
+        const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
+        const int nw = (int)((blockDim.x + 63) >> 6);
+        const uint64_t lt = (1ull << lane) - 1ull;
+        const uint64_t a0 = __ballot(a & 1), a1 = __ballot(a & 2), a2 = __ballot(a & 4);
+        const uint64_t b0 = __ballot(b & 1), b1 = __ballot(b & 2), b2 = __ballot(b & 4);
+        __syncthreads();  // scratch may still be read by the previous call
+        if (lane == 0) {
+            scratch[wid] = __popcll(a0) + 2 * __popcll(a1) + 4 * __popcll(a2);
+            scratch[8 + wid] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+        }
+        __syncthreads();
+        int pa = 0, pb = 0, sa = 0, sb = 0;
+        for (int w = 0; w < nw; ++w) {
+            const int x = scratch[w], y = scratch[8 + w];
+            pa += (w < wid) ? x : 0;
+            pb += (w < wid) ? y : 0;
+            sa += x;
+            sb += y;
+        }
+        *ta = sa;
+        *tb = sb;
+        return make_int2(pa + __popcll(a0 & lt) + 2 * __popcll(a1 & lt) + 4 * __popcll(a2 & lt),
+                         pb + __popcll(b0 & lt) + 2 * __popcll(b1 & lt) + 4 * __popcll(b2 & lt));
+    }
     // block-wide exclusive scans of two 0/1 flags with one pair of barriers (<= 8 waves)
     __device__ int2 scan_pair(int a, int b, int* ta, int* tb) {
         const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
@@ -269,6 +304,12 @@ struct SerialPolicy {
         *ta = a;
         *tb = b;
         return make_int2(0, 0);
+    }
+    __host__ __device__ int2 scan_small2(int a, int b, int* ta, int* tb) { return scan_pair(a, b, ta, tb); }
+    __host__ __device__ int wave_count(bool f) const { return f ? 1 : 0; }
+    template <class T>
+    __host__ __device__ void wave_add2(T ptr, int lo, int hi) {
+        *ptr += (unsigned long long)(uint32_t)lo | ((unsigned long long)(uint32_t)hi << 32);
     }
     __host__ __device__ unsigned long long now() const { return 0; }
     __host__ __device__ int popc64(uint64_t x) const {

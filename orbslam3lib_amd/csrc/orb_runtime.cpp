@@ -43,6 +43,7 @@ const KnobDef kKnobTable[] = {
     {"ORBGPU_OCT_GENERIC", [](DiagKnobs& k, const char*) { k.geom.oct_generic = true; }},
     {"ORBGPU_OCT_PYR",
      [](DiagKnobs& k, const char* v) { k.geom.oct_pyr_max = std::max(0, std::min(kOctPyrMaxD, atoi(v))); }},
+    {"ORBGPU_OCT_ROUNDS", [](DiagKnobs& k, const char* v) { k.geom.oct_rounds = atoi(v) != 0; }},
     {"ORBGPU_FAST_PITCH", [](DiagKnobs& k, const char* v) {  // force the larger tiles
          const int P = atoi(v);
          k.geom.fast_min_tier = P == kCellMax ? 2 : P == kCellPitchSmall ? 1 : 0;
@@ -745,12 +746,16 @@ int orbgpu_synchronize(orbgpu_ctx* c) {
         std::vector<unsigned long long> d((size_t)n * kMaxLevels * 8);
         D2H(d.data(), c->octdbg.p, d.size() * 8);
         for (int l = 0; l < L; ++l) {
-            double acc[8] = {};
-            for (int i = 0; i < n; ++i)
-                for (int k = 0; k < 8; ++k) acc[k] += (double)d[((size_t)i * kMaxLevels + l) * 8 + k];
-            fprintf(stderr, "octree L%d us: init %.1f choose %.1f barrier %.1f sort %.1f rebuild %.1f relabel(pyramid: gather+histogram) %.1f best(pyramid: sums) %.1f rounds %.1f\n",
+            double acc[8] = {}, phase1 = 0;
+            for (int i = 0; i < n; ++i) {
+                const unsigned long long* s = &d[((size_t)i * kMaxLevels + l) * 8];
+                for (int k = 0; k < 7; ++k) acc[k] += (double)s[k];
+                acc[7] += (double)(s[7] & 0xFFFFFFFFull);  // slot 7: rounds, the phase-1 ones in the upper half
+                phase1 += (double)(s[7] >> 32);
+            }
+            fprintf(stderr, "octree L%d us: init %.1f choose %.1f barrier %.1f sort %.1f rebuild(direct phase 1: list build) %.1f relabel(pyramid: gather+histogram) %.1f best(pyramid: sums) %.1f rounds %.1f phase-1 rounds %.1f\n",
                     l, acc[0] / n / 100, acc[1] / n / 100, acc[2] / n / 100, acc[3] / n / 100,
-                    acc[4] / n / 100, acc[5] / n / 100, acc[6] / n / 100, acc[7] / n);
+                    acc[4] / n / 100, acc[5] / n / 100, acc[6] / n / 100, acc[7] / n, phase1 / n);
         }
     }
     return ORBGPU_OK;

@@ -1,4 +1,8 @@
-"""Diagnostic: run one 64-pair batch with ORBGPU_OCT_STAMPS=1 to print octree phase times."""
+"""Diagnostic: run one 64-pair batch with ORBGPU_OCT_STAMPS=1 to print octree phase times.
+
+The slots are named in the printed line (orbgpu_synchronize); with the direct phase 1 the
+"rebuild" slot holds its list build beside the final phase's rebuilds, and "choose" stays empty.
+ORBGPU_OCT_ROUNDS=1 in the environment gives the round-by-round phase 1 for comparison."""
 import os, sys
 os.environ["ORBGPU_OCT_STAMPS"] = "1"
 os.environ["ORBGPU_DIAGNOSTICS"] = "1"
