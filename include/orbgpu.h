@@ -295,8 +295,8 @@ int orbgpu_download_projection_matches(orbgpu_ctx* ctx, int frame, int32_t* matc
  * Deviations (the reference reads out of range there): a point whose projection is not finite or
  * whose octave is outside [0, nlevels) is skipped; an event whose bin is outside [0, 30) (angles
  * outside [0, 360)) counts in nmatches but enters no bin.
- * The two-camera branch (:1840-1914) and the relocalisation overload (:1923-2059) have no entry
- * point. */
+ * The two-camera branch (:1840-1914) is orbgpu_track_by_projection_stereo below; only the
+ * relocalisation overload (:1923-2059) has no entry point. */
 typedef struct {
     float pos[3];      /* pMP->GetWorldPos() */
     float angle;       /* LastFrame.mvKeysUn[i].angle */
@@ -322,8 +322,44 @@ int orbgpu_track_by_projection_batch(orbgpu_ctx* ctx, int n_frames, int image_st
                                      const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
                                      const uint8_t* kp_block, int kp_stride, float th, int mono,
                                      int check_orientation, void* stream);
+/* After orbgpu_track_by_projection_stereo: *n_kp = Nleft + Nright and match covers the left
+ * keypoints, then (from Nleft on) the right ones. */
 int orbgpu_download_track_matches(orbgpu_ctx* ctx, int frame, int32_t* match, int cap, int* n_kp,
                                   int* nmatches, int32_t rot_hist[30]);
+
+/* The same search on two-camera frames (CurrentFrame.Nleft != -1, the KannalaBrandt8 rig;
+ * ORBmatcher.cc:1721-1921 with :1840-1914).  Frame f = left image 2f + right image 2f + 1, both
+ * gridded by orbgpu_undistort_grid_batch with no distortion coefficients, as for
+ * orbgpu_search_by_projection_stereo; kp_block ([n_pairs][kp_stride]) and the downloaded match array
+ * cover Nleft + Nright keypoints, left first.  The last frame's points cover its Nleft + Nright
+ * keypoints: octave and angle come from mvKeys[i] or mvKeysRight[i - Nleft].  Per valid point:
+ *   - x3Dc = Tcw * X; invz = 1 / zc < 0 skips the point (both windows);
+ *   - left window: uv = mpCamera->project(x3Dc) (KannalaBrandt8.cpp:61-78, cam_left); outside
+ *     [mnMinX, mnMaxX] x [mnMinY, mnMaxY] skips the point; GetFeaturesInArea(bRight = false) on
+ *     the left grid and mvKeys with the level range of the direction.  If no keypoint passes its
+ *     level and distance tests the point is skipped, right window included (:1778-1779; tested
+ *     before occupancy: a window whose keypoints all hold points is not empty).  No mvuRight test.
+ *     Best distance <= TH_HIGH: match[best] = i, one event;
+ *   - right window: x3Dr = Trl * x3Dc, uv = mpCamera->project(x3Dr) -- the *left* camera model, as
+ *     the reference calls it -- with no bounds, 1/z or empty-window test; the same radius and
+ *     levels; GetFeaturesInArea(bRight = true) on the right grid and mvKeysRight; a second,
+ *     independent event at Nleft + best;
+ *   - one rotation histogram and one three-maxima rejection over the events of both sides.
+ * Pinned choices: KannalaBrandt8::project as restated for orbgpu_fisheye_stereo_batch (atan2f, cosf
+ * and sinf as the host libm computes them); Trl * x3Dc row by row as ((R0 x + R1 y) + R2 z) + t
+ * (Sophus's own order is not reproducible here).  Parity with the reference is unpinned, as for
+ * the pinhole form.  Deviations: the pinhole form's apply to the point as a whole (left projection
+ * not finite, octave outside [0, nlevels), bin outside [0, 30)); a right projection that is not
+ * finite skips the right window only. */
+typedef struct {
+    float cam_left[8];     /* CurrentFrame.mpCamera: KannalaBrandt8 mvParameters fx fy cx cy k0..k3 */
+    float Rrl[9], trl[3];  /* CurrentFrame.GetRelativePoseTrl() (mTrl), row-major */
+} orbgpu_track_rig;        /* 80 bytes */
+
+int orbgpu_track_by_projection_stereo(orbgpu_ctx* ctx, int n_pairs, const orbgpu_last_point* pts,
+                                      const int32_t* pt_offsets, const orbgpu_track_pose* poses,
+                                      const orbgpu_track_rig* rig, float mb, const uint8_t* kp_block,
+                                      int kp_stride, float th, int mono, int check_orientation, void* stream);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

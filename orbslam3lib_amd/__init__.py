@@ -37,6 +37,8 @@ LAST_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("octave", 
                              ("desc", "u1", (32,))])
 TRACK_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,))])
 LP_VALID = 1  # ORBGPU_LP_VALID (MP_HAS_OBS is shared)
+# orbgpu_track_rig (80 B): the left KannalaBrandt8 camera (fx fy cx cy k0..k3) and Frame::mTrl, row-major
+TRACK_RIG_DTYPE = np.dtype([("cam_left", "<f4", (8,)), ("Rrl", "<f4", (9,)), ("trl", "<f4", (3,))])
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -60,6 +62,7 @@ EXPORTED = [
     "orbgpu_fisheye_stereo_batch", "orbgpu_download_fisheye", "orbgpu_run_batch_match",
     "orbgpu_diagnostic_knobs", "orbgpu_ingest_images", "orbgpu_export_batch_bytes", "orbgpu_export_batch",
     "orbgpu_get_device", "orbgpu_track_by_projection_batch", "orbgpu_download_track_matches",
+    "orbgpu_track_by_projection_stereo",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -743,9 +746,37 @@ class BatchExtractor:
             _p(Kf), C.c_float(mbf), C.c_float(mb), _p(blk) if blk is not None else None, stride, C.c_float(th),
             int(mono), int(check_orientation), C.c_void_p(stream) if stream else None))
 
+    def track_by_projection_stereo(self, points, poses, rig, mb, kp_block=None, th=15.0, mono=False,
+                                   check_orientation=True, stream=None):
+        """The two-camera form (CurrentFrame.Nleft != -1, ORBmatcher.cc:1721-1921 with :1840-1914)
+        on every stereo pair of the last run() (grids from undistort_grid(K, ())); points and poses
+        as for track_by_projection, the points covering the last frame's Nleft + Nright keypoints;
+        rig: a TRACK_RIG_DTYPE record (cam_left, Rrl, trl); kp_block per pair over Nleft + Nright
+        keypoints.  track_matches(frame) then covers Nleft + Nright keypoints, left first."""
+        pts, off, nf = self._map_point_rows(points, LAST_POINT_DTYPE)
+        ps = np.ascontiguousarray(poses, TRACK_POSE_DTYPE).reshape(-1)
+        if len(ps) != nf:
+            raise ValueError("one pose per frame")
+        rg = None
+        if rig is not None:
+            rg = np.ascontiguousarray(rig, TRACK_RIG_DTYPE).reshape(-1)
+            if len(rg) != 1:
+                raise ValueError("one rig")
+        blk, stride = None, 0
+        if kp_block is not None:
+            stride = max(1, max(len(b) for b in kp_block))
+            blk = np.zeros((nf, stride), np.uint8)
+            for f, b in enumerate(kp_block):
+                blk[f, :len(b)] = b
+        _check(_lib.orbgpu_track_by_projection_stereo(
+            self.ctx.handle, nf, _p(pts) if len(pts) else None, _p(off), _p(ps), _p(rg) if rg is not None else None,
+            C.c_float(mb), _p(blk) if blk is not None else None, stride, C.c_float(th), int(mono),
+            int(check_orientation), C.c_void_p(stream) if stream else None))
+
     def track_matches(self, frame, cap=65536):
         """(match [n_kp] int32: last-frame point index or -1, nmatches, rot_hist [30] int32: the bin
-        sizes before the three-maxima rule) of frame `frame`."""
+        sizes before the three-maxima rule) of frame `frame`; n_kp = Nleft + Nright after
+        track_by_projection_stereo."""
         m = np.zeros(cap, np.int32)
         h = np.zeros(30, np.int32)
         n, nm = C.c_int(0), C.c_int(0)

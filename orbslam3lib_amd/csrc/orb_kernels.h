@@ -407,6 +407,20 @@ struct TrackArgs {
 };
 size_t track_resolve_lds_bytes(int out_cap);
 hipError_t launch_track(const TrackArgs& a, int nframes, int max_pts, hipStream_t st);
+// The two-camera branch (Nleft != -1, :1840-1914): frame f = images 2f (left) and 2f + 1 (right),
+// image_step = 2, uright = nullptr; kp_block / match are [frame][2 * out_cap], the left keypoints,
+// then (from Nleft on) the right ones; cand is [2 * point]: frame f's left records at
+// 2 * pt_off[f], its right records after them.
+struct TrackRig {  // orbgpu_track_rig (80 B)
+    float cam[8];  // the left camera's KannalaBrandt8 parameters: both windows project with it
+    float Rrl[9], trl[3];
+};
+struct TrackStereoArgs : TrackArgs {
+    TrackRig rig;
+    uint32_t* side_mask;  // [frame][2 * out_cap] bins of each keypoint's events (match's layout)
+    int32_t* side_hist;   // [frame][2][kRotBins + 1] each side's bin sizes, then its event count
+};
+hipError_t launch_track_stereo(const TrackStereoArgs& a, int npairs, int max_pts, hipStream_t st);
 
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);

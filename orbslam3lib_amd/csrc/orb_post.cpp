@@ -666,17 +666,22 @@ int orbgpu_download_projection_matches(orbgpu_ctx* c, int frame, int32_t* match,
 }
 
 // ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (orb_track.hip) --------
-int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step, int use_uright,
-                                     const orbgpu_last_point* pts, const int32_t* pt_offsets,
-                                     const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
-                                     const uint8_t* kp_block, int kp_stride, float th, int mono,
-                                     int check_orientation, void* stream) {
+namespace {
+
+// Shared by the pinhole entry point (K, rig == nullptr) and the two-camera one (rig, K == nullptr:
+// frame f = images 2f and 2f + 1; kp_block and the match array cover Nleft + Nright keypoints).
+int track_run(orbgpu_ctx* c, int n_frames, int image_step, int use_uright, const orbgpu_last_point* pts,
+              const int32_t* pt_offsets, const orbgpu_track_pose* poses, const float* K,
+              const orbgpu_track_rig* rig, float mbf, float mb, const uint8_t* kp_block, int kp_stride, float th,
+              int mono, int check_orientation, void* stream) {
     static_assert(sizeof(orbgpu_last_point) == sizeof(LastPointIn) && sizeof(orbgpu_last_point) == 56,
                   "last point layout");
     static_assert(sizeof(orbgpu_track_pose) == 96, "track pose layout");
-    if (!c || !pt_offsets || !poses || !K || n_frames < 1) return fail(ORBGPU_ERR_INVALID, "null argument");
+    static_assert(sizeof(orbgpu_track_rig) == sizeof(TrackRig) && sizeof(orbgpu_track_rig) == 80, "track rig layout");
+    const bool two_cam = rig != nullptr;
+    if (!c || !pt_offsets || !poses || (!K && !rig) || n_frames < 1) return fail(ORBGPU_ERR_INVALID, "null argument");
     if (image_step != 1 && image_step != 2) return fail(ORBGPU_ERR_INVALID, "image_step must be 1 or 2");
-    if ((n_frames - 1) * image_step + 1 > c->grid_images)
+    if ((n_frames - 1) * image_step + (two_cam ? 2 : 1) > c->grid_images)
         return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
     if (use_uright && (image_step != 2 || n_frames > c->stereo_pairs))
         return fail(ORBGPU_ERR_INVALID, "mvuRight needs image_step 2 and a stereo_matches_batch over the pairs");
@@ -704,12 +709,15 @@ int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step
         T.pad[0] = T.pad[1] = T.pad[2] = 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = (size_t)c->plan.out_cap;
+    const size_t cap = two_cam ? 2 * (size_t)c->plan.out_cap : (size_t)c->plan.out_cap;
+    const size_t sides = two_cam ? 2 : 1;  // candidate records per point
     if (c->trkpt.ensure((size_t)total * sizeof(LastPointIn) + 256) || c->trkoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
         c->trkframe.ensure((size_t)n_frames * sizeof(TrackFrame) + 256) ||
-        c->trkcand.ensure((size_t)total * sizeof(TrackCand) + 256) || c->trkmatch.ensure((size_t)n_frames * cap * 4 + 256) ||
+        c->trkcand.ensure(sides * total * sizeof(TrackCand) + 256) || c->trkmatch.ensure((size_t)n_frames * cap * 4 + 256) ||
         c->trknm.ensure((size_t)n_frames * (1 + kRotBins) * 4 + 256) ||
-        (kp_block && c->trkblk.ensure((size_t)n_frames * cap + 256)))
+        (kp_block && c->trkblk.ensure((size_t)n_frames * cap + 256)) ||
+        (two_cam && (c->trkmask.ensure((size_t)n_frames * cap * 4 + 256) ||
+                     c->trkside.ensure((size_t)n_frames * 2 * (kRotBins + 1) * 4 + 256))))
         return fail(ORBGPU_ERR_HIP, "hipMalloc failed (motion-model search)");
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     int r = join_all(c, s);  // keypoints, grid and mvuRight come from the chunk streams
@@ -723,7 +731,7 @@ int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step
         HIP_TRY(hipMemcpy2DAsync(c->trkblk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), n_frames,
                                  hipMemcpyHostToDevice, s));
     }
-    TrackArgs a{};
+    TrackStereoArgs a{};
     a.pts = c->trkpt.as<LastPointIn>();
     a.pt_off = c->trkoff.as<int32_t>();
     a.frames = c->trkframe.as<TrackFrame>();
@@ -742,35 +750,70 @@ int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step
     std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
     for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
     a.nlevels = c->prm.nlevels;
-    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
+    for (int k = 0; k < 4; ++k) a.K[k] = K ? K[k] : 0.f;
     a.mbf = mbf;
     a.th = th;
     a.check_orientation = check_orientation != 0;
     a.match = c->trkmatch.as<int32_t>();
     a.nmatches = c->trknm.as<int32_t>();
     a.rot_hist = a.nmatches + n_frames;
-    r = timed(c, ST_SBP, s, [&] { return launch_track(a, n_frames, max_pts, s); });
+    if (two_cam) {
+        std::memcpy(&a.rig, rig, sizeof a.rig);
+        a.side_mask = c->trkmask.as<uint32_t>();
+        a.side_hist = c->trkside.as<int32_t>();
+    }
+    r = timed(c, ST_SBP, s, [&] {
+        return two_cam ? launch_track_stereo(a, n_frames, max_pts, s)
+                       : launch_track(static_cast<const TrackArgs&>(a), n_frames, max_pts, s);
+    });
     if (r) return r;
     HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
     c->trk_frames = n_frames;
     c->trk_step = image_step;
+    c->trk_two_cam = two_cam;
     c->need_fork = true;
     return ORBGPU_OK;
+}
+
+}  // namespace
+
+int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step, int use_uright,
+                                     const orbgpu_last_point* pts, const int32_t* pt_offsets,
+                                     const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
+                                     const uint8_t* kp_block, int kp_stride, float th, int mono,
+                                     int check_orientation, void* stream) {
+    if (!K) return fail(ORBGPU_ERR_INVALID, "null argument");
+    return track_run(c, n_frames, image_step, use_uright, pts, pt_offsets, poses, K, nullptr, mbf, mb, kp_block,
+                     kp_stride, th, mono, check_orientation, stream);
+}
+
+int orbgpu_track_by_projection_stereo(orbgpu_ctx* c, int n_pairs, const orbgpu_last_point* pts,
+                                      const int32_t* pt_offsets, const orbgpu_track_pose* poses,
+                                      const orbgpu_track_rig* rig, float mb, const uint8_t* kp_block, int kp_stride,
+                                      float th, int mono, int check_orientation, void* stream) {
+    if (!rig) return fail(ORBGPU_ERR_INVALID, "null argument");
+    return track_run(c, n_pairs, 2, 0, pts, pt_offsets, poses, nullptr, rig, 0.f, mb, kp_block, kp_stride, th, mono,
+                     check_orientation, stream);
 }
 
 int orbgpu_download_track_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp, int* nmatches,
                                   int32_t rot_hist[30]) {
     if (!c || frame < 0 || frame >= c->trk_frames) return fail(ORBGPU_ERR_INVALID, "bad frame");
     if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    int32_t nk = 0, nm = 0;
-    D2H(&nk, c->outn.as<int32_t>() + (size_t)frame * c->trk_step, 4);
+    int32_t nks[2] = {0, 0}, nm = 0;
+    D2H(nks, c->outn.as<int32_t>() + (size_t)frame * c->trk_step, c->trk_two_cam ? 8 : 4);
     D2H(&nm, c->trknm.as<int32_t>() + frame, 4);
-    if (int e = count_status(nk)) return e;
+    if (int e = count_status(nks[0])) return e;
+    if (c->trk_two_cam)
+        if (int e = count_status(nks[1])) return e;
+    if (!c->trk_two_cam) nks[1] = 0;
+    const int nk = nks[0] + nks[1];  // two-camera frames: Nleft + Nright, the right ones from Nleft on
     if (n_kp) *n_kp = nk;
     if (nmatches) *nmatches = nm;
     if (rot_hist) D2H(rot_hist, c->trknm.as<int32_t>() + c->trk_frames + (size_t)frame * kRotBins, 4 * kRotBins);
     if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    if (match && nk) D2H(match, c->trkmatch.as<int32_t>() + (size_t)frame * c->plan.out_cap, 4 * (size_t)nk);
+    const size_t ncap = c->trk_two_cam ? 2 * (size_t)c->plan.out_cap : (size_t)c->plan.out_cap;
+    if (match && nk) D2H(match, c->trkmatch.as<int32_t>() + (size_t)frame * ncap, 4 * (size_t)nk);
     return ORBGPU_OK;
 }
 

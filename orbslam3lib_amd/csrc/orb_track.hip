@@ -29,8 +29,11 @@
 // Deviations from the reference, which reads out of range in these cases: a point whose projection
 // is not finite, or whose octave is outside [0, nlevels), is skipped; an event whose bin falls
 // outside [0, 30) (angles outside [0, 360) or not finite) counts in nmatches but enters no bin.
+//
+// The two-camera branch (Nleft != -1, :1840-1914) follows the pinhole kernels below.
 #include <hip/hip_runtime.h>
 
+#include "orb_kb8.h"
 #include "orb_kernels.h"
 #include "orb_window.h"
 
@@ -116,20 +119,38 @@ __global__ __launch_bounds__(256) void k_track_candidates(TrackArgs a) {
 // per-keypoint tables (owner, writer, bin mask, match) and the histogram (+ the rejected set).
 __host__ __device__ inline int track_lds_words(int n) { return (n + 31) / 32 + 4 * n + kRotBins + 2; }
 
-__global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const int ncap = a.out_cap;
-    const int nbits = (ncap + 31) / 32;
-    uint32_t* taken = lds;                 // keypoint held by a point with observations
-    uint32_t* owner = taken + nbits;       // lowest pending lane with observations assigning it
-    int32_t* writer = reinterpret_cast<int32_t*>(owner + ncap);  // last committing lane assigning it
-    uint32_t* binmask = reinterpret_cast<uint32_t*>(writer + ncap);  // bins of the keypoint's events
-    int32_t* matchl = reinterpret_cast<int32_t*>(binmask + ncap);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(matchl + ncap);  // [kRotBins], then the rejected set
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const int nk = min(max(a.out_n[f * a.image_step], 0), ncap);
-    const int m0 = a.pt_off[f], m1 = a.pt_off[f + 1];
-    const uint8_t* blk = a.kp_block ? a.kp_block + (long long)f * ncap : nullptr;
+struct ReplayLds {
+    uint32_t* taken;    // keypoint held by a point with observations
+    uint32_t* owner;    // lowest pending lane with observations assigning it
+    int32_t* writer;    // last committing lane assigning it
+    uint32_t* binmask;  // bins of the keypoint's events
+    int32_t* matchl;
+    uint32_t* hist;     // [kRotBins], then the rejected set and its size
+};
+__device__ inline ReplayLds replay_lds(uint32_t* lds, int ncap) {
+    ReplayLds L;
+    L.taken = lds;
+    L.owner = L.taken + (ncap + 31) / 32;
+    L.writer = reinterpret_cast<int32_t*>(L.owner + ncap);
+    L.binmask = reinterpret_cast<uint32_t*>(L.writer + ncap);
+    L.matchl = reinterpret_cast<int32_t*>(L.binmask + ncap);
+    L.hist = reinterpret_cast<uint32_t*>(L.matchl + ncap);
+    return L;
+}
+
+// The sequential loop of one frame (pinhole) or of one side of a two-camera frame, by one wave:
+// the frame's (side's) nk keypoints F with their pre-call occupancy blk, its npts candidate
+// records and points.  Leaves the pre-rejection match, the bin masks and the histogram in LDS and
+// returns the number of events.
+template <class Args>
+__device__ inline int track_replay(const Args& a, const FrameView& F, const ReplayLds& L, const TrackCand* cand,
+                                   const LastPointIn* pts, int npts, int nk, const uint8_t* blk, int dir, int lane) {
+    uint32_t* taken = L.taken;
+    uint32_t* owner = L.owner;
+    int32_t* writer = L.writer;
+    uint32_t* binmask = L.binmask;
+    int32_t* matchl = L.matchl;
+    uint32_t* hist = L.hist;
     for (int w = lane; w < (nk + 31) / 32; w += 64) {
         uint32_t bits = 0;
         if (blk)
@@ -144,17 +165,15 @@ __global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
     }
     if (lane < kRotBins + 2) hist[lane] = 0;
     __syncthreads();
-    const FrameView F = track_view(a, f);
-    const int dir = a.frames[f].dir;
     auto is_taken = [&](int k) { return ((taken[k >> 5] >> (k & 31)) & 1u) != 0; };
     const uint64_t below = (1ull << lane) - 1;
     int events = 0;
-    for (int g0 = m0; g0 < m1; g0 += 64) {
+    for (int g0 = 0; g0 < npts; g0 += 64) {
         const int i = g0 + lane;
-        bool pending = i < m1;
+        bool pending = i < npts;
         TrackCand c{};
         c.n = -1;
-        if (pending) c = a.cand[i];
+        if (pending) c = cand[i];
         pending = pending && c.n > 0;  // skipped points and empty windows assign nothing
         const bool obs = pending && (c.flags & kMpHasObs) != 0;
         while (__ballot(pending)) {
@@ -180,7 +199,7 @@ __global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
                 int minLevel, maxLevel;
                 track_levels(dir, octave, &minLevel, &maxLevel);
                 uint32_t q[8];
-                load_desc(a.pts[__shfl(i, src)].desc, q);
+                load_desc(pts[__shfl(i, src)].desc, q);
                 int wi;
                 const int wd = walk_window_wave(a, F, u, v, minLevel, maxLevel, a.th * a.scale[octave], u - a.mbf * invz,
                                                 q, is_taken, lane, &wi);
@@ -213,7 +232,7 @@ __global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
             __syncthreads();
             if (ev) writer[ak] = -1;
             if (last) {
-                matchl[ak] = i - m0;
+                matchl[ak] = i;
                 if (obs) atomicOr(&taken[ak >> 5], 1u << (ak & 31));
             }
             if (ev && a.check_orientation) {  // :1829-1837
@@ -232,43 +251,196 @@ __global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
             __syncthreads();
         }
     }
-    // ComputeThreeMaxima (:2061-2102) and the rejection (:1697-1716)
+    return events;
+}
+
+// ComputeThreeMaxima (:2061-2102) on hist[0 .. kRotBins) by one lane: hist[kRotBins] = the set of
+// bins the rejection (:1697-1716) clears, hist[kRotBins + 1] = the events in them.
+__device__ inline void three_maxima_reject(uint32_t* hist) {
+    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+    for (int b = 0; b < kRotBins; ++b) {
+        const int s = (int)hist[b];
+        if (s > max1) {
+            max3 = max2, max2 = max1, max1 = s;
+            ind3 = ind2, ind2 = ind1, ind1 = b;
+        } else if (s > max2) {
+            max3 = max2, max2 = s;
+            ind3 = ind2, ind2 = b;
+        } else if (s > max3) {
+            max3 = s, ind3 = b;
+        }
+    }
+    if ((float)max2 < 0.1f * (float)max1) {
+        ind2 = -1, ind3 = -1;
+    } else if ((float)max3 < 0.1f * (float)max1) {
+        ind3 = -1;
+    }
+    uint32_t rej = 0;
+    int dropped = 0;
+    for (int b = 0; b < kRotBins; ++b)
+        if (b != ind1 && b != ind2 && b != ind3) rej |= 1u << b, dropped += (int)hist[b];
+    hist[kRotBins] = rej;
+    hist[kRotBins + 1] = (uint32_t)dropped;
+}
+
+__global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int ncap = a.out_cap;
+    const ReplayLds L = replay_lds(lds, ncap);
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int nk = min(max(a.out_n[f * a.image_step], 0), ncap);
+    const int m0 = a.pt_off[f], m1 = a.pt_off[f + 1];
+    const uint8_t* blk = a.kp_block ? a.kp_block + (long long)f * ncap : nullptr;
+    const int events =
+        track_replay(a, track_view(a, f), L, a.cand + m0, a.pts + m0, m1 - m0, nk, blk, a.frames[f].dir, lane);
     int nmatches = events;
     if (a.check_orientation) {
-        if (lane == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < kRotBins; ++b) {
-                const int s = (int)hist[b];
-                if (s > max1) {
-                    max3 = max2, max2 = max1, max1 = s;
-                    ind3 = ind2, ind2 = ind1, ind1 = b;
-                } else if (s > max2) {
-                    max3 = max2, max2 = s;
-                    ind3 = ind2, ind2 = b;
-                } else if (s > max3) {
-                    max3 = s, ind3 = b;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                ind2 = -1, ind3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            uint32_t rej = 0;
-            int dropped = 0;
-            for (int b = 0; b < kRotBins; ++b)
-                if (b != ind1 && b != ind2 && b != ind3) rej |= 1u << b, dropped += (int)hist[b];
-            hist[kRotBins] = rej;
-            hist[kRotBins + 1] = (uint32_t)dropped;
-        }
+        if (lane == 0) three_maxima_reject(L.hist);
+        __syncthreads();
+        nmatches -= (int)L.hist[kRotBins + 1];
+    }
+    const uint32_t rej = L.hist[kRotBins];
+    int32_t* match = a.match + (long long)f * ncap;
+    for (int k = lane; k < nk; k += 64) match[k] = (L.binmask[k] & rej) ? -1 : L.matchl[k];
+    if (lane < kRotBins) a.rot_hist[f * kRotBins + lane] = (int32_t)L.hist[lane];
+    if (lane == 0) a.nmatches[f] = nmatches;
+}
+
+// ---- the two-camera branch (CurrentFrame.Nleft != -1, :1840-1914) --------------------------------
+// Frame f = left image 2f + right image 2f + 1.  A point's left window (the pinhole rules, with the
+// KannalaBrandt8 projection and without the mvuRight test) and its right window (the point moved
+// by Trl, projected with the *left* camera model as the reference does, no bounds / 1/z test) are
+// separate events on disjoint keypoint ranges, and the left result never feeds the right window:
+// the two sides are independent sequential chains, coupled by the static "left window
+// geometrically empty -> point skipped" rule (:1778-1779), the shared histogram and nmatches.
+//   k_track_candidates_stereo  two adjacent lanes per point (side = lane & 1): both transform the
+//                       point, each projects and walks its side's window; the left lane's skip
+//                       decision reaches the right lane by __shfl_xor.
+//   k_track_resolve_stereo     one wave per (frame, side): track_replay on that side; writes the
+//                       pre-rejection match, the bin masks, the side's histogram and event count.
+//   k_track_finish_stereo      one workgroup per frame: adds the histograms, three maxima, clears
+//                       every keypoint whose mask meets a rejected bin.
+// Trl * x3Dc is evaluated as ((R0 x + R1 y) + R2 z) + t per row: Sophus's own order is not
+// reproducible here, this one is the pinned choice.
+
+__global__ __launch_bounds__(256) void k_track_candidates_stereo(TrackStereoArgs a) {
+    const int f = blockIdx.y;
+    const int m0 = a.pt_off[f], np = a.pt_off[f + 1] - m0;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int side = t & 1, j = t >> 1;
+    if (j >= np) return;  // both lanes of a pair leave together
+    const LastPointIn p = a.pts[m0 + j];
+    TrackCand c;
+#pragma unroll
+    for (int s = 0; s < kTop; ++s) c.idx[s] = -1, c.dist[s] = 256;
+    c.n = -1;
+    c.flags = p.flags;
+    c.octave = p.octave;
+    c.u = c.v = c.invz = 0.f;
+    c.angle = p.angle;
+    c.pad = 0;
+    const TrackFrame T = a.frames[f];
+    const float X = p.pos[0], Y = p.pos[1], Z = p.pos[2];
+    const float xc = ((T.Rcw[0] * X + T.Rcw[1] * Y) + T.Rcw[2] * Z) + T.tcw[0];
+    const float yc = ((T.Rcw[3] * X + T.Rcw[4] * Y) + T.Rcw[5] * Z) + T.tcw[1];
+    const float zc = ((T.Rcw[6] * X + T.Rcw[7] * Y) + T.Rcw[8] * Z) + T.tcw[2];
+    const float invz = 1.0f / zc;
+    const float* R = a.rig.Rrl;
+    float x3[3];
+    x3[0] = side ? ((R[0] * xc + R[1] * yc) + R[2] * zc) + a.rig.trl[0] : xc;
+    x3[1] = side ? ((R[3] * xc + R[4] * yc) + R[5] * zc) + a.rig.trl[1] : yc;
+    x3[2] = side ? ((R[6] * xc + R[7] * yc) + R[8] * zc) + a.rig.trl[2] : zc;
+    float uv[2];
+    kb8_project(a.rig.cam, x3, uv);
+    const float u = uv[0], v = uv[1];
+    const bool finite = isfinite(u) && isfinite(v);
+    const bool octave_ok = p.octave >= 0 && p.octave < a.nlevels;
+    // the point as a whole: the left lane's tests (the right lane's copy of them is overwritten)
+    bool skip = !(p.flags & kLpValid) || invz < 0 || !octave_ok || !finite || u < a.bounds[0] || u > a.bounds[1] ||
+                v < a.bounds[2] || v > a.bounds[3];
+    const bool skip_left = __shfl_xor((int)skip, 1) != 0;
+    if (side) skip = skip_left;
+    const int nkL = min(max(a.out_n[2 * f], 0), a.out_cap);
+    const uint8_t* blk = a.kp_block ? a.kp_block + 2LL * f * a.out_cap + (side ? nkL : 0) : nullptr;
+    int seen = 0;  // keypoints that pass GetFeaturesInArea's level and distance tests
+    if (!skip && (side == 0 || finite)) {
+        const float radius = a.th * a.scale[p.octave];
+        int minLevel, maxLevel;
+        track_levels(T.dir, p.octave, &minLevel, &maxLevel);
+        const FrameView F = frame_view_of(a, 2 * f + side, nullptr);
+        uint32_t q[8];
+        load_desc(p.desc, q);
+        c.n = 0;
+        walk_window(a, F, u, v, minLevel, maxLevel, radius, 0.f, q,
+                    [&](int k) {
+                        ++seen;
+                        return blk && blk[k];
+                    },
+                    [&](int k, int d, int) {
+                        ++c.n;
+                        bool shift = false;  // (distance, window position) order: after equal distances
+#pragma unroll
+                        for (int s = 0; s < kTop; ++s) {
+                            shift = shift || d < c.dist[s];
+                            if (shift) {
+                                const int ti = c.idx[s], td = c.dist[s];
+                                c.idx[s] = k, c.dist[s] = d;
+                                k = ti, d = td;
+                            }
+                        }
+                    });
+        c.u = u, c.v = v;
+    }
+    // :1778-1779: an empty left window (before occupancy) skips the point, right window included
+    const int seen_left = __shfl_xor(seen, 1);
+    if (side && seen_left == 0) {
+#pragma unroll
+        for (int s = 0; s < kTop; ++s) c.idx[s] = -1, c.dist[s] = 256;
+        c.n = -1;
+    }
+    a.cand[2LL * m0 + (long long)side * np + j] = c;
+}
+
+__global__ __launch_bounds__(64) void k_track_resolve_stereo(TrackStereoArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int ncap = a.out_cap;
+    const ReplayLds L = replay_lds(lds, ncap);
+    const int f = blockIdx.x, side = blockIdx.y, lane = threadIdx.x;
+    const int nkL = min(max(a.out_n[2 * f], 0), ncap);
+    const int nk = side ? min(max(a.out_n[2 * f + 1], 0), ncap) : nkL;
+    const long long row = 2LL * f * ncap + (side ? nkL : 0);  // of kp_block, match and side_mask
+    const int m0 = a.pt_off[f], np = a.pt_off[f + 1] - m0;
+    const uint8_t* blk = a.kp_block ? a.kp_block + row : nullptr;
+    const int events = track_replay(a, frame_view_of(a, 2 * f + side, nullptr), L, a.cand + 2LL * m0 + (long long)side * np,
+                                    a.pts + m0, np, nk, blk, a.frames[f].dir, lane);
+    for (int k = lane; k < nk; k += 64) {
+        a.match[row + k] = L.matchl[k];
+        a.side_mask[row + k] = L.binmask[k];
+    }
+    int32_t* h = a.side_hist + (2LL * f + side) * (kRotBins + 1);
+    if (lane < kRotBins) h[lane] = (int32_t)L.hist[lane];
+    if (lane == kRotBins) h[lane] = events;
+}
+
+__global__ __launch_bounds__(256) void k_track_finish_stereo(TrackStereoArgs a) {
+    __shared__ uint32_t hist[kRotBins + 2];
+    const int f = blockIdx.x, t = threadIdx.x;
+    const int32_t* h = a.side_hist + 2LL * f * (kRotBins + 1);
+    if (t < kRotBins + 2) hist[t] = t < kRotBins ? (uint32_t)(h[t] + h[kRotBins + 1 + t]) : 0u;
+    __syncthreads();
+    int nmatches = h[kRotBins] + h[2 * kRotBins + 1];
+    if (a.check_orientation) {
+        if (t == 0) three_maxima_reject(hist);
         __syncthreads();
         nmatches -= (int)hist[kRotBins + 1];
+        const uint32_t rej = hist[kRotBins];
+        const int n = min(max(a.out_n[2 * f], 0), a.out_cap) + min(max(a.out_n[2 * f + 1], 0), a.out_cap);
+        const long long row = 2LL * f * a.out_cap;
+        for (int k = t; k < n; k += 256)
+            if (a.side_mask[row + k] & rej) a.match[row + k] = -1;
     }
-    const uint32_t rej = hist[kRotBins];
-    int32_t* match = a.match + (long long)f * ncap;
-    for (int k = lane; k < nk; k += 64) match[k] = (binmask[k] & rej) ? -1 : matchl[k];
-    if (lane < kRotBins) a.rot_hist[f * kRotBins + lane] = (int32_t)hist[lane];
-    if (lane == 0) a.nmatches[f] = nmatches;
+    if (t < kRotBins) a.rot_hist[f * kRotBins + t] = (int32_t)hist[t];
+    if (t == 0) a.nmatches[f] = nmatches;
 }
 
 }  // namespace
@@ -286,6 +458,21 @@ hipError_t launch_track(const TrackArgs& a, int nframes, int max_pts, hipStream_
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_track_resolve, dim3(nframes), dim3(64), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_stereo(const TrackStereoArgs& a, int npairs, int max_pts, hipStream_t st) {
+    if (npairs <= 0) return hipSuccess;
+    if (max_pts > 0)
+        hipLaunchKernelGGL(k_track_candidates_stereo, dim3((2 * max_pts + 255) / 256, npairs), dim3(256), 0, st, a);
+    const size_t lds = track_resolve_lds_bytes(a.out_cap);  // one side's keypoints per workgroup
+    if (lds > 65536) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_track_resolve_stereo),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_track_resolve_stereo, dim3(npairs, 2), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(k_track_finish_stereo, dim3(npairs), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
