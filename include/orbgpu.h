@@ -361,6 +361,52 @@ int orbgpu_track_by_projection_stereo(orbgpu_ctx* ctx, int n_pairs, const orbgpu
                                       const orbgpu_track_rig* rig, float mb, const uint8_t* kp_block,
                                       int kp_stride, float th, int mono, int check_orientation, void* stream);
 
+/* ---- ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) -----
+ * Tracking::MonocularInitialization's matcher (cpp/src/ORBmatcher.cc:649-764 with
+ * ComputeThreeMaxima :2061-2102; the reference calls it with windowSize 100 on ORBmatcher(0.9,
+ * true)) over pairs of batch images {F1, F2}, both inside the range of the last
+ * orbgpu_undistort_grid_batch.  One image may be F1, or F2, of several pairs (one initial frame
+ * against successive current frames), and F1 == F2 is legal.  All arithmetic is IEEE single,
+ * evaluated in the reference's order:
+ *   1. vnMatches12 has F1's N1 entries, all -1; vMatchedDistance and vnMatches21 have F2's N2
+ *      entries, INT_MAX and -1 (:652-660).
+ *   2. i1 ascending; a keypoint with octave > 0 is skipped (:662-667).
+ *   3. F2.GetFeaturesInArea(prev[i1].x, prev[i1].y, (float)windowSize, 0, 0) (:669, Frame.cc:
+ *      673-739): only octave-0 keypoints of F2, fabs(dx) < r && fabs(dy) < r on mvKeysUn, in the
+ *      order grid column, row, index within the cell; an empty window skips the point (:671-672).
+ *   4. per candidate i2 in that order: skipped when vMatchedDistance[i2] <= dist (:688-689);
+ *      otherwise best / second best with strict < from INT_MAX (:691-700), i.e. the two lowest
+ *      (distance, window position) that survive; an equal distance becomes the second best.
+ *   5. an event when bestDist <= TH_LOW = 50 and (float)bestDist < (float)bestDist2 * nnratio
+ *      (:703-705; a lone candidate has bestDist2 = INT_MAX = 2147483648.0f): the previous owner of
+ *      the keypoint is robbed (vnMatches12[owner] = -1, nmatches--, :707-711), then vnMatches12[i1]
+ *      = best, vnMatches21[best] = i1, vMatchedDistance[best] = bestDist, nmatches++ (:712-715);
+ *      with check_orientation, rot = F1.angle[i1] - F2.angle[best] (+360 if negative), bin =
+ *      round(rot * (1.0f / 30)) (30 -> 0), and i1 enters that bin (:717-727).  The entry of a
+ *      point robbed later stays in its bin and counts towards its size.
+ *   6. ComputeThreeMaxima on the 30 bin sizes; every entry of a bin outside the three that is
+ *      still matched is cleared and takes one off nmatches (:733-756): an entry already robbed
+ *      subtracts nothing.
+ *   7. prev[i1] = F2.mvKeysUn[vnMatches12[i1]].pt wherever vnMatches12[i1] >= 0 (:759-761).
+ * Deviations (the reference reads out of range there): a point whose prev is not finite is
+ * skipped; an event whose bin falls outside [0, 30) counts in nmatches, enters no bin and cannot
+ * be rejected.  Parity with the reference is unpinned, as for the other matcher functions: the
+ * yardstick is the Python restatement in tests/test_search_for_initialization.py.
+ * image_pairs: [n_pairs][2] batch images (host); prev_matched: [n_pairs][pm_stride][2] (host;
+ * NULL: F1's mvKeysUn.pt, the reference's state at the first call).  ORBGPU_ERR_INVALID: null
+ * context, n_pairs < 0 or above the context's image capacity, an image outside the gridded range,
+ * window_size < 0, pm_stride below an F1's keypoint count; n_pairs == 0 succeeds.
+ * ORBGPU_ERR_CAPACITY when the context's keypoint capacity exceeds the matcher's LDS budget, as
+ * for orbgpu_track_by_projection_batch.
+ * orbgpu_download_initialization_matches: match12 [N1] = vnMatches12, prev_matched [N1][2] =
+ * vbPrevMatched after the call (may be NULL), *nmatches = the reference's return value, rot_hist =
+ * the 30 bin sizes before the three-maxima rule (all 0 when check_orientation == 0). */
+int orbgpu_search_for_initialization_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* image_pairs,
+                                           const float* prev_matched, int pm_stride, int window_size,
+                                           float nnratio, int check_orientation, void* stream);
+int orbgpu_download_initialization_matches(orbgpu_ctx* ctx, int pair, int32_t* match12, float* prev_matched,
+                                           int cap, int* n1, int* nmatches, int32_t rot_hist[30]);
+
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,
  * ORBextractor.cc:131-143; DSP split orbslam_dsp.cpp:643-648): frame f's left half (columns

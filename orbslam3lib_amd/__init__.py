@@ -62,7 +62,8 @@ EXPORTED = [
     "orbgpu_fisheye_stereo_batch", "orbgpu_download_fisheye", "orbgpu_run_batch_match",
     "orbgpu_diagnostic_knobs", "orbgpu_ingest_images", "orbgpu_export_batch_bytes", "orbgpu_export_batch",
     "orbgpu_get_device", "orbgpu_track_by_projection_batch", "orbgpu_download_track_matches",
-    "orbgpu_track_by_projection_stereo",
+    "orbgpu_track_by_projection_stereo", "orbgpu_search_for_initialization_batch",
+    "orbgpu_download_initialization_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -782,6 +783,42 @@ class BatchExtractor:
         n, nm = C.c_int(0), C.c_int(0)
         _check(_lib.orbgpu_download_track_matches(self.ctx.handle, frame, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
         return m[:n.value], nm.value, h
+
+    def search_for_initialization(self, image_pairs, prev_matched=None, window_size=100, nnratio=0.9,
+                                  check_orientation=True, stream=None):
+        """ORBmatcher(nnratio, check_orientation).SearchForInitialization(F1, F2, vbPrevMatched,
+        vnMatches12, windowSize) (ORBmatcher.cc:649-764, Tracking::MonocularInitialization) for pairs
+        (F1, F2) of batch images after undistort_grid(); prev_matched: a list (one per pair) of
+        [n1, 2] float32 arrays, or one padded [n_pairs, stride, 2] array; None: F1's mvKeysUn.pt."""
+        pairs = np.ascontiguousarray(image_pairs, np.int32).reshape(-1, 2)
+        pm, stride = None, 0
+        if prev_matched is not None:
+            if isinstance(prev_matched, np.ndarray) and prev_matched.ndim == 3:
+                pm = np.ascontiguousarray(prev_matched, np.float32)
+            else:
+                rows = [np.asarray(r, np.float32).reshape(-1, 2) for r in prev_matched]
+                pm = np.zeros((len(rows), max([1] + [len(r) for r in rows]), 2), np.float32)
+                for p, r in enumerate(rows):
+                    pm[p, :len(r)] = r
+            if pm.shape[0] != len(pairs) or pm.shape[2] != 2:
+                raise ValueError("one row of [n1, 2] points per pair")
+            stride = pm.shape[1]
+        _check(_lib.orbgpu_search_for_initialization_batch(
+            self.ctx.handle, len(pairs), _p(pairs) if len(pairs) else None, _p(pm) if pm is not None else None,
+            stride, int(window_size), C.c_float(nnratio), int(check_orientation),
+            C.c_void_p(stream) if stream else None))
+
+    def initialization_matches(self, pair, cap=65536):
+        """(match12 [n1] int32: vnMatches12, prev_matched [n1, 2] float32: vbPrevMatched after the
+        call, nmatches, rot_hist [30] int32: the bin sizes before the three-maxima rule) of pair
+        `pair` of the last search_for_initialization."""
+        m = np.zeros(cap, np.int32)
+        pm = np.zeros((cap, 2), np.float32)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_initialization_matches(self.ctx.handle, pair, _p(m), _p(pm), cap, C.byref(n),
+                                                           C.byref(nm), _p(h)))
+        return m[:n.value], pm[:n.value], nm.value, h
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

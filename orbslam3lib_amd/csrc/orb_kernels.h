@@ -422,6 +422,44 @@ struct TrackStereoArgs : TrackArgs {
 };
 hipError_t launch_track_stereo(const TrackStereoArgs& a, int npairs, int max_pts, hipStream_t st);
 
+// ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (orb_init.hip).
+constexpr int kInitTop = 4;
+struct InitCand {  // k_init_candidates -> k_init_replay, one per searched F1 keypoint in index order
+    int32_t idx[kInitTop];   // the lowest (distance, window position) candidates, -1 when fewer
+    int32_t dist[kInitTop];
+    int32_t n;               // keypoints of the window that passed GetFeaturesInArea
+    int32_t i1;              // the F1 keypoint
+    int32_t pad[2];
+};
+struct InitArgs {
+    const int32_t* pairs;     // [pair][2]: the batch images F1, F2
+    const float* prev;        // [pair][out_cap][2] vbPrevMatched, or nullptr: F1's mvKeysUn.pt
+    InitCand* cand;           // [pair][out_cap]
+    int32_t* nsearch;         // [pair] searched F1 keypoints (zeroed before the launch)
+    // F2's octave-0 keypoints in grid order (k_init_compact): l0_pre[j] = how many of them precede
+    // entry j of cell_idx ([pair][out_cap + 1]); their index, mvKeysUn.pt and descriptor, packed
+    int32_t* l0_pre;
+    int32_t* l0_idx;          // [pair][out_cap]
+    float* l0_xy;             // [pair][out_cap][2]
+    uint8_t* l0_desc;         // [pair][out_cap][32]
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const float* xy_un;       // grid buffers (orbgpu_undistort_grid_batch)
+    const int32_t* cell_start;
+    const int32_t* cell_idx;
+    const uint8_t* desc;      // out_desc
+    float bounds[4], grid_inv[2];
+    float window, nnratio;
+    int check_orientation;
+    int32_t* match12;         // [pair][out_cap]
+    float* prev_out;          // [pair][out_cap][2] vbPrevMatched after the call
+    int32_t* nmatches;        // [pair]
+    int32_t* rot_hist;        // [pair][kRotBins] bin sizes before the three-maxima rule
+};
+size_t init_replay_lds_bytes(int out_cap);
+hipError_t launch_init_search(const InitArgs& a, int npairs, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

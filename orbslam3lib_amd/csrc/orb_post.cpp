@@ -817,6 +817,102 @@ int orbgpu_download_track_matches(orbgpu_ctx* c, int frame, int32_t* match, int 
     return ORBGPU_OK;
 }
 
+// ---- ORBmatcher::SearchForInitialization (orb_init.hip) -----------------------------------------
+int orbgpu_search_for_initialization_batch(orbgpu_ctx* c, int n_pairs, const int32_t* image_pairs,
+                                           const float* prev_matched, int pm_stride, int window_size, float nnratio,
+                                           int check_orientation, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (n_pairs > 0 && !image_pairs) return fail(ORBGPU_ERR_INVALID, "null image pairs");
+    if (window_size < 0) return fail(ORBGPU_ERR_INVALID, "negative window");
+    for (int k = 0; k < 2 * n_pairs; ++k)
+        if (image_pairs[k] < 0 || image_pairs[k] >= c->grid_images)
+            return fail(ORBGPU_ERR_INVALID, "images must lie in the last orbgpu_undistort_grid_batch");
+    if (n_pairs > 0 && init_replay_lds_bytes(c->plan.out_cap) > 160 * 1024)
+        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
+    if (n_pairs == 0) {
+        c->init_pairs.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
+    if (prev_matched) {  // one row of pm_stride points per pair: it must cover F1's keypoints
+        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+        std::vector<int32_t> counts((size_t)c->grid_images);
+        D2H(counts.data(), c->outn.p, counts.size() * 4);
+        for (int p = 0; p < n_pairs; ++p)
+            if (pm_stride < std::min(counts[image_pairs[2 * p]], (int32_t)cap))
+                return fail(ORBGPU_ERR_INVALID, "pm_stride below F1's keypoint count");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->inipair.ensure(np * 12 + 256) || c->inicand.ensure(np * cap * sizeof(InitCand) + 256) ||
+        c->inimatch.ensure(np * cap * 4 + 256) || c->inipout.ensure(np * cap * 8 + 256) ||
+        c->ininm.ensure(np * (1 + kRotBins) * 4 + 256) || c->inil0.ensure(np * (cap + 4) * 48 + 256) ||
+        (prev_matched && c->iniprev.ensure(np * cap * 8 + 256)))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (initialization search)");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int r = join_all(c, s);  // keypoints and grid come from the chunk streams
+    if (r) return r;
+    // host inputs are pageable: copy, then wait so the caller may reuse them on return
+    int32_t* dpairs = c->inipair.as<int32_t>();
+    HIP_TRY(hipMemcpyAsync(dpairs, image_pairs, np * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(dpairs + 2 * np, 0, np * 4, s));  // the searched-keypoint counts
+    if (prev_matched) {
+        const size_t w = std::min((size_t)pm_stride, cap) * 8;
+        if (w)
+            HIP_TRY(hipMemcpy2DAsync(c->iniprev.p, cap * 8, prev_matched, (size_t)pm_stride * 8, w, np,
+                                     hipMemcpyHostToDevice, s));
+    }
+    InitArgs a{};
+    a.pairs = dpairs;
+    a.prev = prev_matched ? c->iniprev.as<float>() : nullptr;
+    a.cand = c->inicand.as<InitCand>();
+    a.nsearch = dpairs + 2 * np;
+    a.l0_desc = c->inil0.as<uint8_t>();
+    a.l0_xy = reinterpret_cast<float*>(a.l0_desc + np * cap * 32);
+    a.l0_idx = reinterpret_cast<int32_t*>(a.l0_xy + np * cap * 2);
+    a.l0_pre = a.l0_idx + np * cap;
+    a.kps = c->outkps.p;
+    a.out_n = c->outn.as<int32_t>();
+    a.out_cap = c->plan.out_cap;
+    a.xy_un = c->gxy.as<float>();
+    a.cell_start = c->gstart.as<int32_t>();
+    a.cell_idx = c->gidx.as<int32_t>();
+    a.desc = c->outdesc.as<uint8_t>();
+    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
+    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
+    a.window = (float)window_size;
+    a.nnratio = nnratio;
+    a.check_orientation = check_orientation != 0;
+    a.match12 = c->inimatch.as<int32_t>();
+    a.prev_out = c->inipout.as<float>();
+    a.nmatches = c->ininm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_pairs;
+    r = timed(c, ST_SBP, s, [&] { return launch_init_search(a, n_pairs, s); });
+    if (r) return r;
+    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
+    c->init_pairs.assign(image_pairs, image_pairs + 2 * np);
+    c->need_fork = true;
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_initialization_matches(orbgpu_ctx* c, int pair, int32_t* match12, float* prev_matched, int cap,
+                                           int* n1, int* nmatches, int32_t rot_hist[30]) {
+    if (!c || pair < 0 || (size_t)pair >= c->init_pairs.size() / 2) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+    const size_t np = c->init_pairs.size() / 2, o = (size_t)pair * c->plan.out_cap;
+    int32_t nk = 0, nm = 0;
+    D2H(&nk, c->outn.as<int32_t>() + c->init_pairs[2 * (size_t)pair], 4);
+    D2H(&nm, c->ininm.as<int32_t>() + pair, 4);
+    if (int e = count_status(nk)) return e;
+    if (n1) *n1 = nk;
+    if (nmatches) *nmatches = nm;
+    if (rot_hist) D2H(rot_hist, c->ininm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
+    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
+    if (match12 && nk) D2H(match12, c->inimatch.as<int32_t>() + o, 4 * (size_t)nk);
+    if (prev_matched && nk) D2H(prev_matched, c->inipout.as<float>() + 2 * o, 8 * (size_t)nk);
+    return ORBGPU_OK;
+}
+
 int orbgpu_image_bounds(int cols, int rows, const float K[4], const float* dist, int ndist, float bounds[4]) {
     if (!K || !bounds || (ndist > 0 && !dist) || ndist < 0) return fail(ORBGPU_ERR_INVALID, "null argument");
     image_bounds_host(cols, rows, K, dist, ndist, bounds);

@@ -254,35 +254,6 @@ __device__ inline int track_replay(const Args& a, const FrameView& F, const Repl
     return events;
 }
 
-// ComputeThreeMaxima (:2061-2102) on hist[0 .. kRotBins) by one lane: hist[kRotBins] = the set of
-// bins the rejection (:1697-1716) clears, hist[kRotBins + 1] = the events in them.
-__device__ inline void three_maxima_reject(uint32_t* hist) {
-    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-    for (int b = 0; b < kRotBins; ++b) {
-        const int s = (int)hist[b];
-        if (s > max1) {
-            max3 = max2, max2 = max1, max1 = s;
-            ind3 = ind2, ind2 = ind1, ind1 = b;
-        } else if (s > max2) {
-            max3 = max2, max2 = s;
-            ind3 = ind2, ind2 = b;
-        } else if (s > max3) {
-            max3 = s, ind3 = b;
-        }
-    }
-    if ((float)max2 < 0.1f * (float)max1) {
-        ind2 = -1, ind3 = -1;
-    } else if ((float)max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-    }
-    uint32_t rej = 0;
-    int dropped = 0;
-    for (int b = 0; b < kRotBins; ++b)
-        if (b != ind1 && b != ind2 && b != ind3) rej |= 1u << b, dropped += (int)hist[b];
-    hist[kRotBins] = rej;
-    hist[kRotBins + 1] = (uint32_t)dropped;
-}
-
 __global__ __launch_bounds__(64) void k_track_resolve(TrackArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int ncap = a.out_cap;

@@ -1,6 +1,7 @@
 // orb_window.h -- Frame::GetFeaturesInArea (Frame.cc:673-739) over a frame whose keypoints,
 // descriptors, grid and mvuRight live in HBM, shared by the two projection searches
-// (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search).
+// (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search) and, with
+// ComputeThreeMaxima, by the initialisation search (orb_init.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,6 +139,35 @@ __device__ inline FrameView frame_view_of(const Args& a, int img, const float* u
     F.desc = a.desc + 32LL * img * a.out_cap;
     F.uright = uright;
     return F;
+}
+
+// ComputeThreeMaxima (ORBmatcher.cc:2061-2102) on hist[0 .. kRotBins) by one lane: hist[kRotBins] = the set of
+// bins the rejection (e.g. :1697-1716) clears, hist[kRotBins + 1] = the events in them.
+__device__ inline void three_maxima_reject(uint32_t* hist) {
+    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+    for (int b = 0; b < kRotBins; ++b) {
+        const int s = (int)hist[b];
+        if (s > max1) {
+            max3 = max2, max2 = max1, max1 = s;
+            ind3 = ind2, ind2 = ind1, ind1 = b;
+        } else if (s > max2) {
+            max3 = max2, max2 = s;
+            ind3 = ind2, ind2 = b;
+        } else if (s > max3) {
+            max3 = s, ind3 = b;
+        }
+    }
+    if ((float)max2 < 0.1f * (float)max1) {
+        ind2 = -1, ind3 = -1;
+    } else if ((float)max3 < 0.1f * (float)max1) {
+        ind3 = -1;
+    }
+    uint32_t rej = 0;
+    int dropped = 0;
+    for (int b = 0; b < kRotBins; ++b)
+        if (b != ind1 && b != ind2 && b != ind3) rej |= 1u << b, dropped += (int)hist[b];
+    hist[kRotBins] = rej;
+    hist[kRotBins + 1] = (uint32_t)dropped;
 }
 
 }  // namespace orbgpu
