@@ -296,7 +296,8 @@ int orbgpu_download_projection_matches(orbgpu_ctx* ctx, int frame, int32_t* matc
  * whose octave is outside [0, nlevels) is skipped; an event whose bin is outside [0, 30) (angles
  * outside [0, 360)) counts in nmatches but enters no bin.
  * The two-camera branch (:1840-1914) is orbgpu_track_by_projection_stereo below; only the
- * relocalisation overload (:1923-2059) has no entry point. */
+ * relocalisation overload (:1923-2059) has no entry point.  (SearchByBoW, further down, is built
+ * for pinhole frames only: its two-camera form is not.) */
 typedef struct {
     float pos[3];      /* pMP->GetWorldPos() */
     float angle;       /* LastFrame.mvKeysUn[i].angle */
@@ -406,6 +407,65 @@ int orbgpu_search_for_initialization_batch(orbgpu_ctx* ctx, int n_pairs, const i
                                            float nnratio, int check_orientation, void* stream);
 int orbgpu_download_initialization_matches(orbgpu_ctx* ctx, int pair, int32_t* match12, float* prev_matched,
                                            int cap, int* n1, int* nmatches, int32_t rot_hist[30]);
+
+/* ---- ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) ----
+ * The matcher of Tracking::TrackReferenceKeyFrame (ORBmatcher(0.7, true)) and of
+ * Tracking::Relocalization (0.75, against every candidate keyframe): cpp/src/ORBmatcher.cc:224-426
+ * with ComputeThreeMaxima :2061-2102, on pinhole frames (F.Nleft == -1, so bestDist1R stays 256 and
+ * the right-camera block :358-387 never fires).  Pair p = a keyframe given by the host (kf_pts
+ * [kf_offsets[p], kf_offsets[p + 1])) and a frame that is image frames[p] of the last
+ * orbgpu_run_batch; several pairs may name the same frame.  The vocabulary stays on the host: the
+ * node of each keypoint -- mFeatVec, as Frame::ComputeBoW / DBoW2::transform with levelsup = 4
+ * compute it -- is an input on both sides.  All arithmetic is IEEE single, evaluated in the
+ * reference's order:
+ *   1. match has F's N entries, all -1 (:228).
+ *   2. the two feature vectors are std::map<NodeId, vector<unsigned>>; a node's list holds keypoint
+ *      indices in ascending order (transform adds feature i in index order).
+ *   3. the merge :245-403 visits the nodes present in both; nodes do not interact.
+ *   4. in a common node, for iKF ascending (:252): a keyframe keypoint without a map point, or with a
+ *      bad one, is skipped (:258-262); F's keypoints of the node are walked in ascending index order,
+ *      one that holds a match is skipped (:279-280); best and second best with strict < from 256 /
+ *      256 (:286-295): an equal distance becomes the second best, never the best.
+ *   5. an event when bestDist1 <= TH_LOW = 50 and (float)bestDist1 < nnratio * (float)bestDist2
+ *      (:328-330; a lone candidate has bestDist2 = 256): match[bestIdxF] = realIdxKF, nmatches++;
+ *      with check_orientation, rot = KF.angle[realIdxKF] - F.angle[bestIdxF] (+360 if negative), bin
+ *      = round(rot * (1.0f / 30)) (30 -> 0), and bestIdxF enters that bin (:339-354).  A keypoint of
+ *      F is never taken twice.
+ *   6. ComputeThreeMaxima on the 30 bin sizes; every entry of a bin outside the three maxima is
+ *      cleared and takes one off nmatches (:405-423).
+ * Deviations: a negative node means "this keypoint is in no node"; an event whose bin falls
+ * outside [0, 30) (angle outside [0, 360) or not finite; the reference asserts) counts in nmatches,
+ * enters no bin and cannot be rejected.  Parity with the reference is unpinned, as for the other
+ * matcher functions: the yardstick is the Python restatement in tests/test_search_by_bow.py.
+ * The frame needs only the last batch's descriptors and angles, not orbgpu_undistort_grid_batch.
+ * f_nodes: [n_pairs][node_stride], the node of keypoint k of pair p's frame at [p][k].  Host arrays
+ * are pageable and may be reused when the call returns.  ORBGPU_ERR_INVALID: null context, n_pairs
+ * < 0 or above the context's image capacity, null arrays when n_pairs > 0, a frame outside the last
+ * batch, kf_offsets not ascending from a value >= 0, node_stride below a frame's keypoint count;
+ * n_pairs == 0 succeeds and leaves no pair to download.  ORBGPU_ERR_CAPACITY when a pair has more
+ * than ORBGPU_BOW_MAX_POINTS keyframe points, or the context's keypoint capacity per image exceeds
+ * it: one workgroup orders a side's keypoints by node in LDS (5000 features per image fit).
+ * orbgpu_download_bow_matches: match[k] = index, within the pair's keyframe points, of the point that
+ * ends up in vpMapPointMatches[k], -1 if none; *n_kp = F.N; *nmatches = the reference's return
+ * value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when check_orientation ==
+ * 0).  Errors as for orbgpu_download_initialization_matches.
+ * SearchByBoW on two-camera frames (F.Nleft != -1, :297-324 and :358-387) and SearchByBoW(KeyFrame*,
+ * KeyFrame*) are not built. */
+typedef struct {
+    uint8_t desc[32];  /* pKF->mDescriptors.row(i) */
+    float angle;       /* pKF->mvKeysUn[i].angle */
+    int32_t node;      /* the node of mFeatVec that holds i; < 0: none */
+    int32_t flags;     /* ORBGPU_BOW_HAS_POINT: vpMapPointsKF[i] && !isBad() */
+} orbgpu_bow_point;    /* 44 bytes */
+#define ORBGPU_BOW_HAS_POINT 1
+#define ORBGPU_BOW_MAX_POINTS 8192
+
+int orbgpu_search_by_bow_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames,
+                               const orbgpu_bow_point* kf_pts, const int32_t* kf_offsets,
+                               const int32_t* f_nodes, int node_stride, float nnratio,
+                               int check_orientation, void* stream);
+int orbgpu_download_bow_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int cap, int* n_kp,
+                                int* nmatches, int32_t rot_hist[30]);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

@@ -39,6 +39,10 @@ TRACK_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Rlw",
 LP_VALID = 1  # ORBGPU_LP_VALID (MP_HAS_OBS is shared)
 # orbgpu_track_rig (80 B): the left KannalaBrandt8 camera (fx fy cx cy k0..k3) and Frame::mTrl, row-major
 TRACK_RIG_DTYPE = np.dtype([("cam_left", "<f4", (8,)), ("Rrl", "<f4", (9,)), ("trl", "<f4", (3,))])
+# orbgpu_bow_point (44 B): a keyframe keypoint for search_by_bow
+BOW_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("angle", "<f4"), ("node", "<i4"), ("flags", "<i4")])
+BOW_HAS_POINT = 1  # ORBGPU_BOW_HAS_POINT
+BOW_MAX_POINTS = 8192  # ORBGPU_BOW_MAX_POINTS
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -63,7 +67,7 @@ EXPORTED = [
     "orbgpu_diagnostic_knobs", "orbgpu_ingest_images", "orbgpu_export_batch_bytes", "orbgpu_export_batch",
     "orbgpu_get_device", "orbgpu_track_by_projection_batch", "orbgpu_download_track_matches",
     "orbgpu_track_by_projection_stereo", "orbgpu_search_for_initialization_batch",
-    "orbgpu_download_initialization_matches",
+    "orbgpu_download_initialization_matches", "orbgpu_search_by_bow_batch", "orbgpu_download_bow_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -819,6 +823,53 @@ class BatchExtractor:
         _check(_lib.orbgpu_download_initialization_matches(self.ctx.handle, pair, _p(m), _p(pm), cap, C.byref(n),
                                                            C.byref(nm), _p(h)))
         return m[:n.value], pm[:n.value], nm.value, h
+
+    def search_by_bow(self, frames, kf_points, f_nodes, nnratio=0.7, check_orientation=True, stream=None):
+        """ORBmatcher(nnratio, check_orientation).SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:
+        224-426, Tracking::TrackReferenceKeyFrame / Relocalization; pinhole frames) for pairs of a
+        keyframe and a batch image of the last run(); undistort_grid() is not needed.  frames: the
+        batch image of each pair (one image may serve several pairs); kf_points: a list (one per
+        pair) of BOW_POINT_DTYPE arrays, or (points, offsets) in the C ABI's form; f_nodes: a list of
+        int32 arrays (the node of each keypoint of the pair's frame, < 0: none) or one 2-D array
+        [n_pairs, stride]."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        npairs = len(fr)
+        if isinstance(kf_points, tuple):
+            pts, off = kf_points
+            pts = np.ascontiguousarray(pts, BOW_POINT_DTYPE).reshape(-1)
+            off = np.ascontiguousarray(off, np.int32)
+            if off.ndim != 1 or len(off) != npairs + 1 or off.min() < 0 or off.max() > len(pts):
+                raise ValueError("keyframe offsets: one entry per pair plus one, inside the points")
+        else:
+            if len(kf_points) != npairs:
+                raise ValueError("one array of keyframe points per pair")
+            rows = [np.asarray(r, BOW_POINT_DTYPE).reshape(-1) for r in kf_points]
+            pts = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, BOW_POINT_DTYPE))
+            off = np.zeros(npairs + 1, np.int32)
+            off[1:] = np.cumsum([len(r) for r in rows])
+        if isinstance(f_nodes, np.ndarray) and f_nodes.ndim == 2:
+            nodes = np.ascontiguousarray(f_nodes, np.int32)
+        else:
+            rows = [np.asarray(r, np.int32).reshape(-1) for r in f_nodes]
+            nodes = np.full((len(rows), max([1] + [len(r) for r in rows])), -1, np.int32)
+            for p, r in enumerate(rows):
+                nodes[p, :len(r)] = r
+        if nodes.shape[0] != npairs:
+            raise ValueError("one row of nodes per pair")
+        _check(_lib.orbgpu_search_by_bow_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(pts) if npairs else None,
+            _p(off) if npairs else None, _p(nodes) if npairs else None, nodes.shape[1] if npairs else 0,
+            C.c_float(nnratio), int(check_orientation), C.c_void_p(stream) if stream else None))
+
+    def bow_matches(self, pair, cap=65536):
+        """(match [N] int32: for each keypoint of F the index, within the pair's keyframe points, of
+        the point that ends up in vpMapPointMatches, -1 if none; nmatches; rot_hist [30] int32: the
+        bin sizes before the three-maxima rule) of pair `pair` of the last search_by_bow."""
+        m = np.zeros(cap, np.int32)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_bow_matches(self.ctx.handle, pair, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
+        return m[:n.value], nm.value, h
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

@@ -1,0 +1,334 @@
+// ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>&) (cpp/src/ORBmatcher.cc:
+// 224-426; ComputeThreeMaxima :2061-2102), the matcher of Tracking::TrackReferenceKeyFrame and
+// Tracking::Relocalization, on pinhole frames (F.Nleft == -1), over pairs of a keyframe the host
+// gives (descriptor, angle, vocabulary node and map-point flag per keypoint) and a batch image whose
+// descriptors and angles already live in HBM.  The vocabulary stays on the host: the node of every
+// keypoint (mFeatVec, DBoW2::transform with levelsup = 4) is an input.
+//
+// Only keypoints of the same node are compared (:245-403), and the one sequential rule -- a keypoint
+// of F that holds a match is skipped by every later keyframe keypoint (:279-280) -- couples only the
+// keypoints of one node.  So a pair splits into its common nodes, each a small all-pairs Hamming
+// problem replayed in keyframe index order:
+//   k_bow_group   one workgroup per (pair, side) orders the side's keypoints by (node, index) with
+//                 a bitonic sort of 64-bit keys in LDS -- node ids are arbitrary 31-bit values, so
+//                 there is nothing to count over -- and writes the ordered index list and the node
+//                 segment table.  Keypoints with a negative node drop out here; keyframe keypoints
+//                 without a map point stay in the order (they are skipped at replay).  The frame
+//                 side also packs its descriptors in that order, so that a node's descriptors are
+//                 contiguous, and sets the pair's match row to -1.
+//   k_bow_match   one wave per keyframe node segment.  The frame's segment of the same node is
+//                 found by binary search; lane l holds the frame's descriptors l, l + 64, ... of
+//                 the segment (the first 64 in registers with their index, angle and taken bit,
+//                 the chunks above re-read per keyframe keypoint, their taken bits in LDS).  The
+//                 keyframe's keypoints are staged 64 at a time, one per lane, so that no load
+//                 sits in the sequential chain.  Per keyframe keypoint in index order, its
+//                 descriptor wave-uniform (read from its lane):
+//                 eight popcounts per lane and chunk, the lane's two lowest distance << 16 |
+//                 position keys over the keypoints not taken, two wave reductions for the two lowest
+//                 (the first is bestDist1 / bestIdxF with the reference's strict <, the second is
+//                 bestDist2), one event test per wave; then the taken bit, match and bin are
+//                 written.  A frame keypoint belongs to one node, hence to one wave: no atomics on
+//                 match, and none on the bins: the bin is stored beside the match.  The writes of
+//                 the first 64 keypoints of a segment wait in registers until its chain has ended.
+//   k_bow_finish  one workgroup per pair: the 30 bin sizes are counted from the stored bins (LDS
+//                 integer atomics: order-independent), then three_maxima_reject, the matches whose
+//                 bin is rejected are cleared (:405-423), nmatches is what is left.
+//
+// Deviations from the reference: a negative node means "in no node"; an event whose bin falls
+// outside [0, 30) (the reference asserts) counts in nmatches, enters no bin and cannot be rejected.
+#include <hip/hip_runtime.h>
+
+#include "orb_kernels.h"
+#include "orb_window.h"
+
+namespace orbgpu {
+namespace {
+
+constexpr int kThLow = 50;  // ORBmatcher::TH_LOW
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;
+constexpr uint64_t kNoNode = ~0ull;  // sorts behind every node id
+constexpr int kNoBin = 31;           // an event outside [0, 30), or no orientation check
+constexpr int kGroupThreads = 1024;
+constexpr int kMatchWaves = 128;     // waves per pair in k_bow_match, each striding over the segments (measured:
+                                     // 16 / 32 / 64 / 128 -> 0.228 / 0.218 / 0.208 / 0.199 ms per 256 pairs)
+
+__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// The ordered lists of one (pair, side).
+struct BowSide {
+    int32_t* order;      // keypoint indices by (node, index)
+    int32_t* seg_node;   // node of segment s
+    int32_t* seg_start;  // [segments + 1] into order
+    int n;               // keypoints of the side
+};
+__device__ inline BowSide bow_kf_side(const BowArgs& a, int p) {
+    const int o0 = a.kf_off[p];
+    BowSide s;
+    s.order = a.kf_order + o0;
+    s.seg_node = a.kf_seg_node + o0;
+    s.seg_start = a.kf_seg_start + o0 + p;
+    s.n = clampi(a.kf_off[p + 1] - o0, 0, kBowMaxPoints);
+    return s;
+}
+__device__ inline BowSide bow_f_side(const BowArgs& a, int p) {
+    BowSide s;
+    s.order = a.f_order + (long long)p * a.out_cap;
+    s.seg_node = a.f_seg_node + (long long)p * a.out_cap;
+    s.seg_start = a.f_seg_start + (long long)p * (a.out_cap + 1);
+    s.n = clampi(a.out_n[a.frames[p]], 0, min(a.out_cap, kBowMaxPoints));
+    return s;
+}
+
+__global__ __launch_bounds__(kGroupThreads) void k_bow_group(BowArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t keys[];  // [npad]
+    __shared__ int32_t wsum[kGroupThreads / 64];
+    __shared__ int32_t nvalid;
+    const int p = blockIdx.x, side = blockIdx.y, t = threadIdx.x, cap = a.out_cap;
+    const BowSide S = side == 0 ? bow_kf_side(a, p) : bow_f_side(a, p);
+    const int n = S.n;
+    const BowPoint* kf = a.kf_pts + a.kf_off[p];
+    const int32_t* fnode = a.f_nodes + (long long)p * cap;
+    int npad = 1;
+    while (npad < n) npad <<= 1;  // <= kBowMaxPoints: the launch sized keys[] for it
+    if (t == 0) nvalid = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int j = t; j < npad; j += kGroupThreads) {
+        const int node = j < n ? (side == 0 ? kf[j].node : fnode[j]) : -1;
+        keys[j] = node < 0 ? kNoNode : (((uint64_t)(uint32_t)node << 32) | (uint32_t)j);
+        mine += node >= 0 ? 1 : 0;
+    }
+    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((t & 63) == 0 && mine) atomicAdd(&nvalid, mine);
+    __syncthreads();
+    // bitonic sort, ascending: the keys are distinct but for the padding, which ends up last
+    for (int k = 2; k <= npad; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int q = t; q < (npad >> 1); q += kGroupThreads) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
+                const uint64_t x = keys[i], y = keys[l];
+                if ((x > y) == ((i & k) == 0)) keys[i] = y, keys[l] = x;
+            }
+            __syncthreads();
+        }
+    }
+    const int m = min(nvalid, n);
+    if (side == 1) {  // the call's initial state (:228) and the descriptors in node order
+        int32_t* match = a.match + (long long)p * cap;
+        for (int k = t; k < n; k += kGroupThreads) match[k] = -1;
+        const uint8_t* desc = a.desc + 32LL * a.frames[p] * cap;
+        uint4* packed = reinterpret_cast<uint4*>(a.f_desc + 32LL * p * cap);
+        for (int j = t; j < 2 * m; j += kGroupThreads) {
+            const int k = min((int)(uint32_t)keys[j >> 1], n - 1);
+            packed[j] = reinterpret_cast<const uint4*>(desc + 32LL * k)[j & 1];
+        }
+    }
+    int nseg = 0;
+    for (int j0 = 0; j0 < m; j0 += kGroupThreads) {
+        const int j = j0 + t;
+        const bool valid = j < m;
+        const uint32_t node = valid ? (uint32_t)(keys[j] >> 32) : 0u;
+        const bool head = valid && (j == 0 || (uint32_t)(keys[j - 1] >> 32) != node);
+        const uint64_t bal = __ballot(head);
+        if ((t & 63) == 0) wsum[t >> 6] = __popcll(bal);
+        __syncthreads();
+        int rank = nseg + __popcll(bal & ((1ull << (t & 63)) - 1));
+        for (int w = 0; w < kGroupThreads / 64; ++w) {
+            rank += w < (t >> 6) ? wsum[w] : 0;
+            nseg += wsum[w];
+        }
+        if (valid) S.order[j] = min((int)(uint32_t)keys[j], n - 1);
+        if (head) S.seg_node[rank] = (int32_t)node, S.seg_start[rank] = j;
+        __syncthreads();
+    }
+    if (t == 0) {
+        S.seg_start[nseg] = m;  // nseg <= m <= n: within the side's n + 1 entries
+        a.nseg[2 * p + side] = nseg;
+    }
+}
+
+// An event's writes (:332-354) by the lane that holds frame keypoint idxF: match and the bin of rot =
+// kang - angF.  A frame keypoint is taken once, so k_bow_finish counts the bins from these.
+__device__ inline void bow_commit(const BowArgs& a, int32_t* match, uint8_t* mbin, int idxF, float angF, int kidx,
+                                  float kang) {
+    uint32_t bin = kNoBin;
+    if (a.check_orientation) {
+        float rot = kang - angF;
+        if (rot < 0.0f) rot += 360.0f;
+        const float rb = roundf(rot * (1.0f / 30));
+        if (rb >= 0.f && rb <= 30.f) {
+            bin = (uint32_t)(int)rb;
+            if (bin == kRotBins) bin = 0;
+        }
+    }
+    match[idxF] = kidx;
+    mbin[idxF] = (uint8_t)bin;
+}
+
+// Lane j's value of a wave-uniform j.
+__device__ inline uint32_t lane_value(uint32_t v, int j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, j); }
+
+// The wave's lowest value, to every lane; all 64 lanes must be active.  Within a row of 16 by DPP (lane
+// ^ 1, lane ^ 2, mirror of 8, mirror of 16), then the four rows.
+template <int kCtrl>
+__device__ inline uint32_t dpp_min(uint32_t v) {
+    return min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xF, 0xF, false));
+}
+__device__ inline uint32_t wave_min(uint32_t v) {
+    v = dpp_min<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+    v = dpp_min<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+    v = dpp_min<0x141>(v);  // row_half_mirror
+    v = dpp_min<0x140>(v);  // row_mirror
+    return min(min(lane_value(v, 0), lane_value(v, 16)), min(lane_value(v, 32), lane_value(v, 48)));
+}
+
+__global__ __launch_bounds__(64) void k_bow_match(BowArgs a) {
+    __shared__ uint64_t taken[kBowMaxPoints / 64];  // per 64 positions of the frame's segment, from 64 on
+    const int p = blockIdx.y, lane = threadIdx.x, cap = a.out_cap;
+    const BowSide K = bow_kf_side(a, p), F = bow_f_side(a, p);
+    const int nsegK = clampi(a.nseg[2 * p], 0, K.n), nsegF = clampi(a.nseg[2 * p + 1], 0, F.n);
+    const BowPoint* kf = a.kf_pts + a.kf_off[p];
+    const uint8_t* fdesc = a.f_desc + 32LL * p * cap;
+    const uint8_t* fkps = static_cast<const uint8_t*>(a.kps) + 28LL * a.frames[p] * cap;
+    int32_t* match = a.match + (long long)p * cap;
+    uint8_t* mbin = a.match_bin + (long long)p * cap;
+    for (int s = blockIdx.x; s < nsegK; s += gridDim.x) {
+        const int node = K.seg_node[s];
+        // the frame's segment of the node: halve while the first node >= it lies in [lo, hi], then one
+        // probe per lane
+        int lo = 0, hi = nsegF;
+        while (hi - lo > 63) {
+            const int mid = (lo + hi) >> 1;
+            if (F.seg_node[mid] < node) lo = mid + 1; else hi = mid;
+        }
+        const uint64_t hit = __ballot(lo + lane <= hi && lo + lane < nsegF && F.seg_node[lo + lane] == node);
+        if (!hit) continue;  // a node of the keyframe only
+        lo += __builtin_ctzll(hit);
+        const int ks = clampi(K.seg_start[s], 0, K.n), ke = clampi(K.seg_start[s + 1], ks, K.n);
+        const int fs = clampi(F.seg_start[lo], 0, F.n), nf = clampi(F.seg_start[lo + 1], fs, F.n) - fs;
+        const int nch = (nf + 63) >> 6;
+        if (nch > 1) {
+            __syncthreads();  // the previous segment's last read of taken[]
+            for (int c = 1 + lane; c < nch; c += 64) taken[c] = 0;
+            __syncthreads();
+        }
+        // the frame's first 64 keypoints of the node, one per lane: descriptor, index, angle, taken
+        uint32_t d0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int idx0 = 0;
+        float ang0 = 0.f;
+        bool taken0 = false;
+        int kidx0 = 0;      // the keyframe keypoint that took it, and its angle: written after the loop,
+        float kang0 = 0.f;  // so that the sequential chain of the first 64 holds no memory operation
+        if (lane < nf) {
+            const uint4* d = reinterpret_cast<const uint4*>(fdesc + 32LL * (fs + lane));
+            const uint4 x = d[0], y = d[1];
+            d0[0] = x.x, d0[1] = x.y, d0[2] = x.z, d0[3] = x.w, d0[4] = y.x, d0[5] = y.y, d0[6] = y.z, d0[7] = y.w;
+            idx0 = clampi(F.order[fs + lane], 0, F.n - 1);
+            ang0 = *reinterpret_cast<const float*>(fkps + 28LL * idx0 + 12);
+        }
+        for (int i0 = ks; i0 < ke; i0 += 64) {  // :252, iKF ascending, 64 keyframe keypoints staged per lane
+            uint32_t qd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            int kidx_l = 0, flags_l = 0;
+            float kang_l = 0.f;
+            if (i0 + lane < ke) {
+                kidx_l = clampi(K.order[i0 + lane], 0, K.n - 1);
+                const BowPoint& pt = kf[kidx_l];
+                flags_l = pt.flags, kang_l = pt.angle;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) qd[w] = pt.desc[w];
+            }
+            // (the staged loads land here, not at their first use inside the chain)
+            asm volatile("" ::"v"(qd[0]), "v"(qd[1]), "v"(qd[2]), "v"(qd[3]), "v"(qd[4]), "v"(qd[5]), "v"(qd[6]), "v"(qd[7]),
+                         "v"(kang_l));
+            for (uint64_t todo = __ballot(flags_l & 1); todo; todo &= todo - 1) {  // :258-262 skips the others
+                const int j = __builtin_ctzll(todo);
+                uint32_t q[8];
+#pragma unroll
+                for (int w = 0; w < 8; ++w) q[w] = lane_value(qd[w], j);
+                uint32_t k1 = kNoKey, k2 = kNoKey;  // distance << 16 | position in the segment
+                if (lane < nf && !taken0) {
+                    int dist = 0;
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) dist += __popc(q[w] ^ d0[w]);
+                    k1 = ((uint32_t)dist << 16) | (uint32_t)lane;
+                }
+                for (int c = 1; c < nch; ++c) {
+                    const int pos = c * 64 + lane;
+                    if (pos < nf && !((taken[c] >> lane) & 1ull)) {
+                        const uint32_t key = ((uint32_t)hamming32(q, fdesc + 32LL * (fs + pos)) << 16) | (uint32_t)pos;
+                        k2 = min(k2, max(k1, key));
+                        k1 = min(k1, key);
+                    }
+                }
+                // the wave's two lowest: the second is the lowest once the best's lane gives its own second
+                const uint32_t low = wave_min(k1);
+                k2 = wave_min(k1 == low ? k2 : k1);
+                k1 = low;
+                const int best1 = k1 == kNoKey ? 256 : (int)(k1 >> 16), best2 = k2 == kNoKey ? 256 : (int)(k2 >> 16);
+                const bool ev = best1 <= kThLow && (float)best1 < a.nnratio * (float)best2;  // :328-330
+                const int pos = (int)(k1 & 0xFFFFu);
+                const int kidx = (int)lane_value((uint32_t)kidx_l, j);
+                const float kang = __uint_as_float(lane_value(__float_as_uint(kang_l), j));
+                if (ev && lane == (pos & 63)) {  // the lane that holds the keypoint
+                    if (pos < 64) {
+                        taken0 = true, kidx0 = kidx, kang0 = kang;
+                    } else {
+                        const int idxF = clampi(F.order[fs + pos], 0, F.n - 1);
+                        taken[pos >> 6] |= 1ull << (pos & 63);
+                        bow_commit(a, match, mbin, idxF, *reinterpret_cast<const float*>(fkps + 28LL * idxF + 12), kidx,
+                                   kang);
+                    }
+                }
+                if (nch > 1) __syncthreads();  // one wave: orders the taken bit before the next keypoint's reads
+            }
+        }
+        if (taken0) bow_commit(a, match, mbin, idx0, ang0, kidx0, kang0);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bow_finish(BowArgs a) {
+    __shared__ uint32_t hist[kRotBins + 2];  // the bins, the rejected set, its size
+    __shared__ int32_t wcnt[4];
+    const int p = blockIdx.x, t = threadIdx.x, cap = a.out_cap;
+    const int n = clampi(a.out_n[a.frames[p]], 0, min(cap, kBowMaxPoints));
+    int32_t* match = a.match + (long long)p * cap;
+    const uint8_t* mbin = a.match_bin + (long long)p * cap;
+    if (t < kRotBins + 2) hist[t] = 0;
+    __syncthreads();
+    for (int k = t; k < n; k += 256)  // a keypoint is taken at most once: the bin sizes are those of the matches
+        if (match[k] >= 0 && mbin[k] < kRotBins) atomicAdd(&hist[mbin[k]], 1u);
+    __syncthreads();
+    if (t < kRotBins) a.rot_hist[p * kRotBins + t] = (int32_t)hist[t];
+    if (a.check_orientation && t == 0) three_maxima_reject(hist);  // :405-423
+    __syncthreads();
+    const uint32_t rej = hist[kRotBins];
+    int nm = 0;
+    for (int k = t; k < n; k += 256) {
+        if (match[k] < 0) continue;
+        if ((rej >> (mbin[k] & 31)) & 1u) match[k] = -1; else ++nm;
+    }
+    for (int o = 32; o >= 1; o >>= 1) nm += __shfl_xor(nm, o);
+    if ((t & 63) == 0) wcnt[t >> 6] = nm;
+    __syncthreads();
+    if (t == 0) a.nmatches[p] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+}
+
+}  // namespace
+
+hipError_t launch_bow_search(const BowArgs& a, int npairs, int max_side, hipStream_t st) {
+    if (npairs <= 0) return hipSuccess;
+    int npad = 1;
+    while (npad < max_side) npad <<= 1;
+    const size_t lds = 8 * (size_t)npad;  // max_side <= kBowMaxPoints: at most 64 KiB, beside the static arrays
+    if (lds + 256 > 65536) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_group),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_bow_group, dim3(npairs, 2), dim3(kGroupThreads), lds, st, a);
+    hipLaunchKernelGGL(k_bow_match, dim3(kMatchWaves, npairs), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_bow_finish, dim3(npairs), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace orbgpu

@@ -460,6 +460,42 @@ struct InitArgs {
 size_t init_replay_lds_bytes(int out_cap);
 hipError_t launch_init_search(const InitArgs& a, int npairs, hipStream_t st);
 
+// ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (orb_bow.hip).
+constexpr int kBowMaxPoints = 8192;  // keypoints per side k_bow_group sorts in LDS (ORBGPU_BOW_MAX_POINTS)
+struct BowPoint {  // orbgpu_bow_point
+    uint32_t desc[8];
+    float angle;
+    int32_t node;
+    int32_t flags;
+};
+struct BowArgs {
+    const int32_t* frames;    // [pair] the batch image that is F
+    const BowPoint* kf_pts;   // all pairs' keyframe points, pair p = [kf_off[p], kf_off[p + 1])
+    const int32_t* kf_off;    // [pair + 1], kf_off[0] == 0
+    const int32_t* f_nodes;   // [pair][out_cap] the node of each keypoint of F, < 0: none
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const uint8_t* desc;      // out_desc
+    float nnratio;
+    int check_orientation;
+    // k_bow_group -> k_bow_match: each side's keypoints by (node, index) and its node segments
+    int32_t* kf_order;        // [kf point]
+    int32_t* kf_seg_node;     // [kf point]
+    int32_t* kf_seg_start;    // pair p at kf_off[p] + p, one entry more than its points
+    int32_t* f_order;         // [pair][out_cap]
+    int32_t* f_seg_node;      // [pair][out_cap]
+    int32_t* f_seg_start;     // [pair][out_cap + 1]
+    uint8_t* f_desc;          // [pair][out_cap][32] F's descriptors in f_order's order
+    int32_t* nseg;            // [pair][2] segments of the keyframe, of F
+    int32_t* match;           // [pair][out_cap]
+    uint8_t* match_bin;       // [pair][out_cap] the bin of the event that wrote match
+    int32_t* nmatches;        // [pair]
+    int32_t* rot_hist;        // [pair][kRotBins] bin sizes before the three-maxima rule
+};
+// max_side: the largest keypoint count of a side (<= kBowMaxPoints)
+hipError_t launch_bow_search(const BowArgs& a, int npairs, int max_side, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

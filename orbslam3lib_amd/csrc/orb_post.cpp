@@ -913,6 +913,111 @@ int orbgpu_download_initialization_matches(orbgpu_ctx* c, int pair, int32_t* mat
     return ORBGPU_OK;
 }
 
+// ---- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (orb_bow.hip) -------------------------------
+static_assert(sizeof(orbgpu_bow_point) == 44 && sizeof(BowPoint) == 44, "orbgpu_bow_point is 44 bytes");
+static_assert(ORBGPU_BOW_MAX_POINTS == kBowMaxPoints, "the header states the grouping kernel's limit");
+
+int orbgpu_search_by_bow_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const orbgpu_bow_point* kf_pts,
+                               const int32_t* kf_offsets, const int32_t* f_nodes, int node_stride, float nnratio,
+                               int check_orientation, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !f_nodes)) return fail(ORBGPU_ERR_INVALID, "null array");
+    for (int p = 0; p < n_pairs; ++p)
+        if (frames[p] < 0 || frames[p] >= c->last_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_run_batch");
+    if (n_pairs > 0 && kf_offsets[0] < 0) return fail(ORBGPU_ERR_INVALID, "negative keyframe offset");
+    for (int p = 0; p < n_pairs; ++p)
+        if (kf_offsets[p + 1] < kf_offsets[p]) return fail(ORBGPU_ERR_INVALID, "kf_offsets must ascend");
+    if (n_pairs > 0 && node_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative node_stride");
+    if (n_pairs == 0) {
+        c->bow_frames.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
+    {  // one row of node_stride nodes per pair: it must cover the frame's keypoints
+        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+        std::vector<int32_t> counts((size_t)c->last_images);
+        D2H(counts.data(), c->outn.p, counts.size() * 4);
+        for (int p = 0; p < n_pairs; ++p)
+            if (node_stride < std::min(counts[frames[p]], (int32_t)cap))
+                return fail(ORBGPU_ERR_INVALID, "node_stride below the frame's keypoint count");
+    }
+    int max_side = (int)cap;
+    for (int p = 0; p < n_pairs; ++p) max_side = std::max(max_side, kf_offsets[p + 1] - kf_offsets[p]);
+    if (max_side > kBowMaxPoints)
+        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    // pair p's keyframe points from 0 on the device
+    std::vector<int32_t> head(2 * np + 1);
+    std::copy(frames, frames + np, head.begin());
+    for (size_t p = 0; p <= np; ++p) head[np + p] = kf_offsets[p] - kf_offsets[0];
+    const size_t nkf = (size_t)head[2 * np];
+    HIP_TRY(hipSetDevice(c->device));
+    // bowgrp: kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order, f_seg_node [np * cap
+    // each], f_seg_start [np * (cap + 1)], nseg [2 np]
+    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
+    if (c->bowin.ensure(head.size() * 4 + 256) || c->bowkf.ensure(nkf * sizeof(BowPoint) + 256) ||
+        c->bowfn.ensure(np * cap * 4 + 256) || c->bowgrp.ensure(grp_words * 4 + 256) ||
+        c->bowdesc.ensure(np * cap * 32 + 256) || c->bowmatch.ensure(np * cap * 5 + 256) ||
+        c->bownm.ensure(np * (1 + kRotBins) * 4 + 256))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (bag-of-words search)");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int r = join_all(c, s);  // keypoints and descriptors come from the chunk streams
+    if (r) return r;
+    // host inputs are pageable: copy, then wait so the caller may reuse them on return
+    HIP_TRY(hipMemcpyAsync(c->bowin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
+    if (nkf)
+        HIP_TRY(hipMemcpyAsync(c->bowkf.p, kf_pts + kf_offsets[0], nkf * sizeof(BowPoint), hipMemcpyHostToDevice, s));
+    if (const size_t w = std::min((size_t)node_stride, cap) * 4)
+        HIP_TRY(hipMemcpy2DAsync(c->bowfn.p, cap * 4, f_nodes, (size_t)node_stride * 4, w, np, hipMemcpyHostToDevice, s));
+    BowArgs a{};
+    a.frames = c->bowin.as<int32_t>();
+    a.kf_off = a.frames + np;
+    a.kf_pts = c->bowkf.as<BowPoint>();
+    a.f_nodes = c->bowfn.as<int32_t>();
+    a.kps = c->outkps.p;
+    a.out_n = c->outn.as<int32_t>();
+    a.out_cap = c->plan.out_cap;
+    a.desc = c->outdesc.as<uint8_t>();
+    a.nnratio = nnratio;
+    a.check_orientation = check_orientation != 0;
+    a.kf_order = c->bowgrp.as<int32_t>();
+    a.kf_seg_node = a.kf_order + nkf;
+    a.kf_seg_start = a.kf_seg_node + nkf;
+    a.f_order = a.kf_seg_start + nkf + np;
+    a.f_seg_node = a.f_order + np * cap;
+    a.f_seg_start = a.f_seg_node + np * cap;
+    a.nseg = a.f_seg_start + np * (cap + 1);
+    a.f_desc = c->bowdesc.as<uint8_t>();
+    a.match = c->bowmatch.as<int32_t>();
+    a.match_bin = reinterpret_cast<uint8_t*>(a.match + np * cap);
+    a.nmatches = c->bownm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_pairs;
+    r = timed(c, ST_SBP, s, [&] { return launch_bow_search(a, n_pairs, max_side, s); });
+    if (r) return r;
+    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
+    c->bow_frames.assign(frames, frames + np);
+    c->need_fork = true;
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_bow_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
+                                int32_t rot_hist[30]) {
+    if (!c || pair < 0 || (size_t)pair >= c->bow_frames.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+    const size_t np = c->bow_frames.size(), o = (size_t)pair * c->plan.out_cap;
+    int32_t nk = 0, nm = 0;
+    D2H(&nk, c->outn.as<int32_t>() + c->bow_frames[(size_t)pair], 4);
+    D2H(&nm, c->bownm.as<int32_t>() + pair, 4);
+    if (int e = count_status(nk)) return e;
+    if (n_kp) *n_kp = nk;
+    if (nmatches) *nmatches = nm;
+    if (rot_hist) D2H(rot_hist, c->bownm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
+    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
+    if (match && nk) D2H(match, c->bowmatch.as<int32_t>() + o, 4 * (size_t)nk);
+    return ORBGPU_OK;
+}
+
 int orbgpu_image_bounds(int cols, int rows, const float K[4], const float* dist, int ndist, float bounds[4]) {
     if (!K || !bounds || (ndist > 0 && !dist) || ndist < 0) return fail(ORBGPU_ERR_INVALID, "null argument");
     image_bounds_host(cols, rows, K, dist, ndist, bounds);
