@@ -295,9 +295,9 @@ int orbgpu_download_projection_matches(orbgpu_ctx* ctx, int frame, int32_t* matc
  * Deviations (the reference reads out of range there): a point whose projection is not finite or
  * whose octave is outside [0, nlevels) is skipped; an event whose bin is outside [0, 30) (angles
  * outside [0, 360)) counts in nmatches but enters no bin.
- * The two-camera branch (:1840-1914) is orbgpu_track_by_projection_stereo below; only the
- * relocalisation overload (:1923-2059) has no entry point.  (SearchByBoW, further down, is built
- * for pinhole frames only: its two-camera form is not.) */
+ * The two-camera branch (:1840-1914) is orbgpu_track_by_projection_stereo below; the
+ * relocalisation overload (:1923-2059) is orbgpu_reloc_by_projection_batch, further down.
+ * (SearchByBoW, further down, is built for pinhole frames only: its two-camera form is not.) */
 typedef struct {
     float pos[3];      /* pMP->GetWorldPos() */
     float angle;       /* LastFrame.mvKeysUn[i].angle */
@@ -466,6 +466,76 @@ int orbgpu_search_by_bow_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* fram
                                int check_orientation, void* stream);
 int orbgpu_download_bow_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int cap, int* n_kp,
                                 int* nmatches, int32_t rot_hist[30]);
+
+/* ---- ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) ----
+ * The search Tracking::Relocalization (Tracking.cc:3670-3829) runs on a candidate keyframe when PnP
+ * and pose optimisation left too few inliers, on ORBmatcher(0.9, true) with (th, ORBdist) = (10, 100)
+ * and then (3, 64): cpp/src/ORBmatcher.cc:1923-2059 with ComputeThreeMaxima :2061-2102 and
+ * MapPoint::PredictScale (MapPoint.cc:533-548), pinhole frames, monocular path (mvKeysUn,
+ * GetFeaturesInArea(bRight = false), no mvuRight test).  Pair p = the keyframe points kf_pts
+ * [kf_offsets[p], kf_offsets[p + 1]) in the keyframe's keypoint order, batch image frames[p] inside
+ * the range of the last orbgpu_undistort_grid_batch, pose p and occupancy row p; several pairs may
+ * name the same frame, each with its own pose and occupancy.  All arithmetic is IEEE single,
+ * evaluated in the reference's order.  For i ascending:
+ *   1. a point without ORBGPU_RP_VALID is skipped (:1941-1944).
+ *   2. x3Dc = Tcw * X, row by row as ((R0 x + R1 y) + R2 z) + t; u = fx * xc / zc + cx, v = fy * yc /
+ *      zc + cy (Pinhole.cpp:40-41); skipped when u < mnMinX || u > mnMaxX, likewise v (:1953-1956).
+ *      This overload has no 1/z test.
+ *   3. PO = X - Ow, dist3D = sqrtf((PO.x * PO.x + PO.y * PO.y) + PO.z * PO.z); skipped when dist3D <
+ *      0.8f * min_distance || dist3D > 1.2f * max_distance (:1959-1967, MapPoint.cc:504-514).
+ *   4. ratio = max_distance / dist3D; nPredictedLevel = (int)ceilf(logf(ratio) / logf(scaleFactor))
+ *      clamped to [0, nlevels - 1], logf being the host libm's (orbgpu_predict_scale_table below).
+ *   5. GetFeaturesInArea(u, v, th * mvScaleFactors[level], level - 1, level + 1) (:1972-1974).
+ *   6. over the window, in the order grid column, row, index within the cell: a keypoint that holds
+ *      a point -- before the call, or taken earlier in it -- is skipped (:1988-1989); the best is
+ *      the first lowest Hamming distance, strict < from 256; no second best, no ratio test.
+ *   7. an event when bestDist <= orb_dist: match[best] = i, nmatches++, the keypoint is taken; with
+ *      check_orientation rot = angleKF[i] - angleF[best]; rot < 0 || rot > 360: rot = fmodf(rot,
+ *      360.0f); rot < 0: rot += 360.0f; bin = round(rot * (1.0f / 30)) (30 -> 0) (:2010-2027).
+ *   8. ComputeThreeMaxima on the 30 bin sizes; every entry of a bin outside the three maxima is
+ *      cleared and takes one off nmatches (:2036-2056).
+ * Deviations (the reference reads out of range there): a point whose projection, dist3D or ratio is
+ * not finite is skipped; an event whose bin is outside [0, 30) counts in nmatches, enters no bin and
+ * cannot be rejected.  Parity with the reference is unpinned, as for the other matcher functions:
+ * the yardstick is the Python restatement in tests/test_reloc_projection.py.
+ * kp_block ([n_pairs][kp_stride] u8, host; NULL: none): [p][k] != 0 where CurrentFrame.mvpMapPoints[k]
+ * is set before the call.  K = {fx, fy, cx, cy}.  Host arrays are pageable and may be reused when the
+ * call returns.  ORBGPU_ERR_INVALID: null context, n_pairs < 0 or above the context's image
+ * capacity, null arrays when n_pairs > 0, a frame outside the gridded range, kf_offsets not
+ * ascending from a value >= 0, kp_stride below a frame's keypoint count, orb_dist outside [0, 255]
+ * (256 would assign keypoint -1), th negative or not finite; n_pairs == 0 succeeds and leaves no
+ * pair to download.  ORBGPU_ERR_CAPACITY when the context's keypoint capacity exceeds the matcher's
+ * LDS budget, as for orbgpu_track_by_projection_batch.  Every status is decided before any launch.
+ * orbgpu_download_reloc_matches: match[k] = index, within the pair's keyframe points, of the point
+ * that ends up in CurrentFrame.mvpMapPoints[k] by this call, -1 if none; *n_kp = N; *nmatches = the
+ * reference's return value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when
+ * check_orientation == 0).  Errors as for orbgpu_download_bow_matches. */
+typedef struct {
+    float pos[3];        /* pMP->GetWorldPos() */
+    float angle;         /* pKF->mvKeysUn[i].angle */
+    float min_distance;  /* pMP->mfMinDistance (the 0.8f factor is applied here) */
+    float max_distance;  /* pMP->mfMaxDistance (1.2f for the gate, raw for PredictScale) */
+    int32_t flags;       /* ORBGPU_RP_VALID: pMP && !isBad() && !sAlreadyFound.count(pMP) */
+    uint8_t desc[32];    /* pMP->GetDescriptor() */
+} orbgpu_reloc_point;    /* 60 bytes */
+#define ORBGPU_RP_VALID 1
+typedef struct {
+    float Rcw[9], tcw[3], Ow[3];  /* CurrentFrame.GetPose(), row-major; Tcw.inverse().translation() */
+} orbgpu_reloc_pose;              /* 60 bytes */
+
+int orbgpu_reloc_by_projection_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames,
+                                     const orbgpu_reloc_point* pts, const int32_t* kf_offsets,
+                                     const orbgpu_reloc_pose* poses, const float K[4], const uint8_t* kp_block,
+                                     int kp_stride, float th, int orb_dist, int check_orientation, void* stream);
+int orbgpu_download_reloc_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int cap, int* n_kp,
+                                  int* nmatches, int32_t rot_hist[30]);
+/* The steps of MapPoint::PredictScale as a function of ratio = mfMaxDistance / dist3D (host
+ * computation, no device): thresholds[n], n in [0, nlevels - 1), is the largest float r with
+ * ceilf(logf(r) / logf(scale_factor)) <= n under the host libm, found by bisection over the float's
+ * bit pattern, so that the clamped level is the number of thresholds below ratio.  The device counts
+ * them: its own logf need not equal the host's near a step.  ORBGPU_ERR_INVALID: scale_factor not
+ * above 1, nlevels outside [1, 16], a null table with nlevels > 1. */
+int orbgpu_predict_scale_table(float scale_factor, int nlevels, float* thresholds);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

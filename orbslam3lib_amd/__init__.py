@@ -19,7 +19,8 @@ import os
 import numpy as np
 
 __all__ = ["ORBextractor", "ORBmatcher", "BFMatcher", "BatchExtractor", "KEYPOINT_DTYPE", "MAP_POINT_DTYPE",
-           "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "OrbGpuError", "load_library", "LIB_PATH"]
+           "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "RELOC_POINT_DTYPE", "RELOC_POSE_DTYPE", "predict_scale_table",
+           "OrbGpuError", "load_library", "LIB_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # ORBGPU_LIB names another build of the same library (measurement variants under tools/)
@@ -43,6 +44,12 @@ TRACK_RIG_DTYPE = np.dtype([("cam_left", "<f4", (8,)), ("Rrl", "<f4", (9,)), ("t
 BOW_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("angle", "<f4"), ("node", "<i4"), ("flags", "<i4")])
 BOW_HAS_POINT = 1  # ORBGPU_BOW_HAS_POINT
 BOW_MAX_POINTS = 8192  # ORBGPU_BOW_MAX_POINTS
+# orbgpu_reloc_point (60 B): a keyframe's map point for reloc_by_projection; orbgpu_reloc_pose (60 B):
+# CurrentFrame.GetPose(), row-major, and its camera centre Tcw.inverse().translation()
+RELOC_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("min_distance", "<f4"),
+                              ("max_distance", "<f4"), ("flags", "<i4"), ("desc", "u1", (32,))])
+RELOC_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,))])
+RP_VALID = 1  # ORBGPU_RP_VALID
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -68,6 +75,7 @@ EXPORTED = [
     "orbgpu_get_device", "orbgpu_track_by_projection_batch", "orbgpu_download_track_matches",
     "orbgpu_track_by_projection_stereo", "orbgpu_search_for_initialization_batch",
     "orbgpu_download_initialization_matches", "orbgpu_search_by_bow_batch", "orbgpu_download_bow_matches",
+    "orbgpu_reloc_by_projection_batch", "orbgpu_download_reloc_matches", "orbgpu_predict_scale_table",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -159,6 +167,16 @@ def diagnostic_knobs() -> dict:
     load_library().orbgpu_diagnostic_knobs(buf, len(buf))
     txt = buf.value.decode()
     return dict(kv.split("=", 1) for kv in txt.split(";")) if txt else {}
+
+
+def predict_scale_table(scale_factor, nlevels) -> np.ndarray:
+    """orbgpu_predict_scale_table: float32 [nlevels - 1], entry n the largest ratio = mfMaxDistance /
+    dist3D whose MapPoint::PredictScale (host logf) is at most n.  The clamped level of a ratio is the
+    number of entries below it.  Host computation: no device is needed."""
+    lib = load_library()
+    t = np.zeros(max(int(nlevels) - 1, 0), np.float32)
+    _check(lib.orbgpu_predict_scale_table(C.c_float(scale_factor), int(nlevels), _p(t) if len(t) else None))
+    return t
 
 
 def _check(code):
@@ -869,6 +887,63 @@ class BatchExtractor:
         h = np.zeros(30, np.int32)
         n, nm = C.c_int(0), C.c_int(0)
         _check(_lib.orbgpu_download_bow_matches(self.ctx.handle, pair, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
+        return m[:n.value], nm.value, h
+
+    def reloc_by_projection(self, frames, kf_points, poses, K, kp_block=None, th=10.0, orb_dist=100,
+                            check_orientation=True, stream=None):
+        """ORBmatcher(0.9, check_orientation).SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th,
+        ORBdist) (ORBmatcher.cc:1923-2059, Tracking::Relocalization; pinhole frames) for pairs of a
+        keyframe's map points and a batch image after undistort_grid().  frames: the batch image of
+        each pair (one image may serve several pairs); kf_points: a list (one per pair) of
+        RELOC_POINT_DTYPE arrays, or (points, offsets) in the C ABI's form; poses: RELOC_POSE_DTYPE
+        array, one row per pair; K = (fx, fy, cx, cy); kp_block: optional list (one per pair) of u8
+        arrays, or one 2-D array (non-zero = the keypoint already holds a map point)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        npairs = len(fr)
+        if isinstance(kf_points, tuple):
+            pts, off = kf_points
+            pts = np.ascontiguousarray(pts, RELOC_POINT_DTYPE).reshape(-1)
+            off = np.ascontiguousarray(off, np.int32)
+            if off.ndim != 1 or len(off) != npairs + 1 or off.min() < 0 or off.max() > len(pts):
+                raise ValueError("keyframe offsets: one entry per pair plus one, inside the points")
+        else:
+            if len(kf_points) != npairs:
+                raise ValueError("one array of keyframe points per pair")
+            rows = [np.asarray(r, RELOC_POINT_DTYPE).reshape(-1) for r in kf_points]
+            pts = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, RELOC_POINT_DTYPE))
+            off = np.zeros(npairs + 1, np.int32)
+            off[1:] = np.cumsum([len(r) for r in rows])
+        ps = np.ascontiguousarray(poses, RELOC_POSE_DTYPE).reshape(-1)
+        if len(ps) != npairs:
+            raise ValueError("one pose per pair")
+        Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
+        blk, stride = None, 0
+        if kp_block is not None:
+            if isinstance(kp_block, np.ndarray) and kp_block.ndim == 2:
+                blk = np.ascontiguousarray(kp_block, np.uint8)
+            else:
+                rows = [np.asarray(b, np.uint8).reshape(-1) for b in kp_block]
+                blk = np.zeros((len(rows), max([1] + [len(b) for b in rows])), np.uint8)
+                for p, b in enumerate(rows):
+                    blk[p, :len(b)] = b
+            if blk.shape[0] != npairs:
+                raise ValueError("one row of occupancy per pair")
+            stride = blk.shape[1]
+        _check(_lib.orbgpu_reloc_by_projection_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(pts) if len(pts) else None,
+            _p(off) if npairs else None, _p(ps) if npairs else None, _p(Kf),
+            _p(blk) if blk is not None and npairs else None, stride, C.c_float(th), int(orb_dist),
+            int(check_orientation), C.c_void_p(stream) if stream else None))
+
+    def reloc_matches(self, pair, cap=65536):
+        """(match [N] int32: for each keypoint of the frame the index, within the pair's keyframe
+        points, of the point this call put into mvpMapPoints, -1 if none; nmatches; rot_hist [30]
+        int32: the bin sizes before the three-maxima rule) of pair `pair` of the last
+        reloc_by_projection."""
+        m = np.zeros(cap, np.int32)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_reloc_matches(self.ctx.handle, pair, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
         return m[:n.value], nm.value, h
 
     def undistort_grid(self, K, dist=(), stream=None):

@@ -133,12 +133,14 @@ struct orbgpu_ctx {
         fel2r{bufs}, fer2l{bufs}, fedepth{bufs}, fep3d{bufs}, fecnt{bufs}, trkpt{bufs}, trkoff{bufs}, trkframe{bufs},
         trkcand{bufs}, trkblk{bufs}, trkmatch{bufs}, trknm{bufs}, trkmask{bufs}, trkside{bufs}, inipair{bufs}, iniprev{bufs},
         inicand{bufs}, inil0{bufs}, inimatch{bufs}, inipout{bufs}, ininm{bufs}, bowin{bufs}, bowkf{bufs}, bowfn{bufs},
-        bowgrp{bufs}, bowdesc{bufs}, bowmatch{bufs}, bownm{bufs};
+        bowgrp{bufs}, bowdesc{bufs}, bowmatch{bufs}, bownm{bufs}, relin{bufs}, relpt{bufs}, relpose{bufs},
+        relcand{bufs}, relblk{bufs}, relmatch{bufs}, relnm{bufs};
     float grid_bounds[4] = {0, 0, 0, 0}, grid_inv[2] = {0, 0};  // of the last undistort_grid
     int sbp_frames = 0, sbp_step = 1, sbp_two_cam = 0;
     int trk_frames = 0, trk_step = 1, trk_two_cam = 0;  // coverage of the last orbgpu_track_by_projection_*
     std::vector<int32_t> init_pairs;  // {F1, F2} of the last orbgpu_search_for_initialization_batch
     std::vector<int32_t> bow_frames;  // F of each pair of the last orbgpu_search_by_bow_batch
+    std::vector<int32_t> reloc_frames;  // CurrentFrame of each pair of the last orbgpu_reloc_by_projection_batch
     int soa_images = 0, soa_pairs = 0;  // coverage of the last orbgpu_pack_soa
     int grid_images = 0;   // images of the last orbgpu_undistort_grid_batch
     int stereo_pairs = 0;  // pairs of the last orbgpu_stereo_matches_batch

@@ -496,6 +496,51 @@ struct BowArgs {
 // max_side: the largest keypoint count of a side (<= kBowMaxPoints)
 hipError_t launch_bow_search(const BowArgs& a, int npairs, int max_side, hipStream_t st);
 
+// ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist)
+// (orb_reloc.hip).
+struct RelocPoint {  // orbgpu_reloc_point (60 B)
+    float pos[3], angle, min_distance, max_distance;
+    int32_t flags;
+    uint8_t desc[32];
+};
+constexpr int kRpValid = 1;
+struct RelocPose {  // orbgpu_reloc_pose (60 B)
+    float Rcw[9], tcw[3], Ow[3];
+};
+struct RelocCand {  // k_reloc_candidates -> k_reloc_resolve
+    int32_t idx[4];   // 4 lowest (distance, window position) among those within orb_dist
+    int32_t dist[4];
+    int32_t n;        // candidates within orb_dist after the filters; -1: point skipped
+    int32_t level;    // nPredictedLevel
+    float u, v;       // the projection (:1951)
+};
+struct RelocArgs {
+    const int32_t* frames;    // [pair] the batch image that is CurrentFrame
+    const RelocPoint* pts;    // all pairs' keyframe points, pair p = [kf_off[p], kf_off[p + 1])
+    const int32_t* kf_off;    // [pair + 1], kf_off[0] == 0
+    const RelocPose* poses;   // [pair]
+    RelocCand* cand;          // [point]
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const float* xy_un;       // grid buffers (orbgpu_undistort_grid_batch)
+    const int32_t* cell_start;
+    const int32_t* cell_idx;
+    const uint8_t* desc;      // out_desc
+    const uint8_t* kp_block;  // [pair][out_cap] mvpMapPoints[k] set before the call, or nullptr
+    float bounds[4], grid_inv[2];
+    float scale[kMaxLevels];
+    float level_step[kMaxLevels];  // predict_scale_table: level = #{n < nlevels - 1 : ratio > level_step[n]}
+    int nlevels;
+    float K[4], th;
+    int orb_dist, check_orientation;
+    int32_t* match;           // [pair][out_cap]
+    int32_t* nmatches;        // [pair]
+    int32_t* rot_hist;        // [pair][kRotBins] bin sizes before the three-maxima rule
+};
+size_t reloc_resolve_lds_bytes(int out_cap);
+hipError_t launch_reloc(const RelocArgs& a, int npairs, int max_pts, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

@@ -1018,6 +1018,155 @@ int orbgpu_download_bow_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap
     return ORBGPU_OK;
 }
 
+// ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (orb_reloc.hip) ----
+static_assert(sizeof(orbgpu_reloc_point) == 60 && sizeof(RelocPoint) == 60, "orbgpu_reloc_point is 60 bytes");
+static_assert(sizeof(orbgpu_reloc_pose) == 60 && sizeof(RelocPose) == 60, "orbgpu_reloc_pose is 60 bytes");
+
+namespace {
+
+// MapPoint::PredictScale before its clamps (MapPoint.cc:541): log(float) is the host libm's logf
+int predicted_scale(float ratio, float log_scale) { return (int)std::ceil(std::log(ratio) / log_scale); }
+
+// thresholds[n] = the largest float r with ceilf(logf(r) / logf(scale_factor)) <= n, by bisection over the
+// bit patterns of the positive floats (the step function is monotone in r)
+void predict_scale_table(float scale_factor, int nlevels, float* thresholds) {
+    const float log_scale = std::log(scale_factor);
+    auto as_float = [](uint32_t b) {
+        float f;
+        std::memcpy(&f, &b, 4);
+        return f;
+    };
+    for (int n = 0; n + 1 < nlevels; ++n) {
+        uint32_t lo = 0x00000001u, hi = 0x7F7FFFFFu;  // the predicate holds at lo
+        if (predicted_scale(as_float(hi), log_scale) <= n) lo = hi;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (predicted_scale(as_float(mid), log_scale) <= n) lo = mid; else hi = mid;
+        }
+        thresholds[n] = as_float(lo);
+    }
+}
+
+}  // namespace
+
+int orbgpu_predict_scale_table(float scale_factor, int nlevels, float* thresholds) {
+    if (!(scale_factor > 1.0f) || !std::isfinite(scale_factor) || nlevels < 1 || nlevels > kMaxLevels ||
+        (nlevels > 1 && !thresholds))
+        return fail(ORBGPU_ERR_INVALID, "scale_factor above 1, nlevels in [1, 16] and a table of nlevels - 1 entries");
+    predict_scale_table(scale_factor, nlevels, thresholds);
+    return ORBGPU_OK;
+}
+
+int orbgpu_reloc_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const orbgpu_reloc_point* pts,
+                                     const int32_t* kf_offsets, const orbgpu_reloc_pose* poses, const float K[4],
+                                     const uint8_t* kp_block, int kp_stride, float th, int orb_dist,
+                                     int check_orientation, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (orb_dist < 0 || orb_dist > 255) return fail(ORBGPU_ERR_INVALID, "orb_dist outside [0, 255]");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ORBGPU_ERR_INVALID, "th negative or not finite");
+    if (n_pairs > 0 && (!frames || !kf_offsets || !poses || !K)) return fail(ORBGPU_ERR_INVALID, "null array");
+    for (int p = 0; p < n_pairs; ++p)
+        if (frames[p] < 0 || frames[p] >= c->grid_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
+    if (n_pairs > 0 && kf_offsets[0] < 0) return fail(ORBGPU_ERR_INVALID, "negative keyframe offset");
+    int max_pts = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (kf_offsets[p + 1] < kf_offsets[p]) return fail(ORBGPU_ERR_INVALID, "kf_offsets must ascend");
+        max_pts = std::max(max_pts, kf_offsets[p + 1] - kf_offsets[p]);
+    }
+    if (n_pairs > 0 && kf_offsets[n_pairs] > kf_offsets[0] && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
+    if (n_pairs > 0 && kp_block && kp_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative kp_stride");
+    if (n_pairs > 0 && reloc_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
+        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
+    if (n_pairs == 0) {
+        c->reloc_frames.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
+    if (kp_block) {  // one row of kp_stride flags per pair: it must cover the frame's keypoints
+        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+        std::vector<int32_t> counts((size_t)c->grid_images);
+        D2H(counts.data(), c->outn.p, counts.size() * 4);
+        for (int p = 0; p < n_pairs; ++p)
+            if (kp_stride < std::min(counts[frames[p]], (int32_t)cap))
+                return fail(ORBGPU_ERR_INVALID, "kp_stride below the frame's keypoint count");
+    }
+    // pair p's points from 0 on the device
+    std::vector<int32_t> head(2 * np + 1);
+    std::copy(frames, frames + np, head.begin());
+    for (size_t p = 0; p <= np; ++p) head[np + p] = kf_offsets[p] - kf_offsets[0];
+    const size_t total = (size_t)head[2 * np];
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->relin.ensure(head.size() * 4 + 256) || c->relpt.ensure(total * sizeof(RelocPoint) + 256) ||
+        c->relpose.ensure(np * sizeof(RelocPose) + 256) || c->relcand.ensure(total * sizeof(RelocCand) + 256) ||
+        c->relmatch.ensure(np * cap * 4 + 256) || c->relnm.ensure(np * (1 + kRotBins) * 4 + 256) ||
+        (kp_block && c->relblk.ensure(np * cap + 256)))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (relocalisation search)");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int r = join_all(c, s);  // keypoints and grid come from the chunk streams
+    if (r) return r;
+    // host inputs are pageable: copy, then wait so the caller may reuse them on return
+    HIP_TRY(hipMemcpyAsync(c->relin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
+    if (total)
+        HIP_TRY(hipMemcpyAsync(c->relpt.p, pts + kf_offsets[0], total * sizeof(RelocPoint), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->relpose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
+    if (kp_block) {
+        HIP_TRY(hipMemsetAsync(c->relblk.p, 0, np * cap, s));
+        if (const size_t w = std::min((size_t)kp_stride, cap))
+            HIP_TRY(hipMemcpy2DAsync(c->relblk.p, cap, kp_block, kp_stride, w, np, hipMemcpyHostToDevice, s));
+    }
+    RelocArgs a{};
+    a.frames = c->relin.as<int32_t>();
+    a.kf_off = a.frames + np;
+    a.pts = c->relpt.as<RelocPoint>();
+    a.poses = c->relpose.as<RelocPose>();
+    a.cand = c->relcand.as<RelocCand>();
+    a.kps = c->outkps.p;
+    a.out_n = c->outn.as<int32_t>();
+    a.out_cap = c->plan.out_cap;
+    a.xy_un = c->gxy.as<float>();
+    a.cell_start = c->gstart.as<int32_t>();
+    a.cell_idx = c->gidx.as<int32_t>();
+    a.desc = c->outdesc.as<uint8_t>();
+    a.kp_block = kp_block ? c->relblk.as<uint8_t>() : nullptr;
+    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
+    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
+    for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
+    a.nlevels = c->prm.nlevels;
+    predict_scale_table(c->prm.scale_factor, c->prm.nlevels, a.level_step);  // Frame.cc:132 + MapPoint.cc:541
+    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
+    a.th = th;
+    a.orb_dist = orb_dist;
+    a.check_orientation = check_orientation != 0;
+    a.match = c->relmatch.as<int32_t>();
+    a.nmatches = c->relnm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_pairs;
+    r = timed(c, ST_SBP, s, [&] { return launch_reloc(a, n_pairs, max_pts, s); });
+    if (r) return r;
+    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
+    c->reloc_frames.assign(frames, frames + np);
+    c->need_fork = true;
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_reloc_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
+                                  int32_t rot_hist[30]) {
+    if (!c || pair < 0 || (size_t)pair >= c->reloc_frames.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
+    const size_t np = c->reloc_frames.size(), o = (size_t)pair * c->plan.out_cap;
+    int32_t nk = 0, nm = 0;
+    D2H(&nk, c->outn.as<int32_t>() + c->reloc_frames[(size_t)pair], 4);
+    D2H(&nm, c->relnm.as<int32_t>() + pair, 4);
+    if (int e = count_status(nk)) return e;
+    if (n_kp) *n_kp = nk;
+    if (nmatches) *nmatches = nm;
+    if (rot_hist) D2H(rot_hist, c->relnm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
+    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
+    if (match && nk) D2H(match, c->relmatch.as<int32_t>() + o, 4 * (size_t)nk);
+    return ORBGPU_OK;
+}
+
 int orbgpu_image_bounds(int cols, int rows, const float K[4], const float* dist, int ndist, float bounds[4]) {
     if (!K || !bounds || (ndist > 0 && !dist) || ndist < 0) return fail(ORBGPU_ERR_INVALID, "null argument");
     image_bounds_host(cols, rows, K, dist, ndist, bounds);

@@ -257,3 +257,89 @@ def last_frame_points(xy_un, kps, desc, K, pose, uright=None, n=1000, seed=0, mb
             d[i] = np.packbits(b)
     out["desc"] = d
     return out
+
+
+def reloc_points(xy_un, kps, desc, K, pose, n=1000, seed=0, th=10.0, bounds=(0.0, 640.0, 0.0, 480.0), pool=None,
+                 nlevels=8, scale_factor=1.2, invalid=0.05, outside=0.04, too_near=0.03, too_far=0.03,
+                 not_finite=0.01, level_offsets=(-1, 0, 0, 0, 1), over_top=0.02, wild_angles=0.02,
+                 flips=(0, 2, 5, 10, 20, 35, 50, 80, 120)):
+    """Synthetic keyframe points for the relocalisation SearchByProjection (a RELOC_POINT_DTYPE
+    array): the frame's keypoints (xy_un, kps: KEYPOINT_DTYPE, desc) unprojected at random depths
+    through the inverse of pose = (Rcw 3x3, tcw 3), with sub-radius position noise, `flips` flipped
+    descriptor bits and the keypoint's angle plus a common offset and small noise.  The level
+    MapPoint::PredictScale gives is steered through max_distance: the distance to the camera centre
+    is max_distance / scale_factor ** (level - 0.5), level = the keypoint's octave plus one of
+    `level_offsets` (a ratio in (1 / 1.2, 1] for level 0), and for a share `over_top` the ratio lies
+    above the last step, where the level is clamped; min_distance = max_distance / scale_factor **
+    (nlevels - 1).  Several points aim at each of `pool` keypoints (default n // 2).  Mixed in by the
+    given shares: invalid points, projections outside the bounds (every side in turn), points nearer
+    than 0.8 min_distance, farther than 1.2 max_distance, not finite (position, a position that
+    overflows the distance, an infinite max_distance, in turn), and angles moved by +-720 degrees
+    (`wild_angles`; 10% of the angles are random)."""
+    from . import RELOC_POINT_DTYPE, RP_VALID
+    rng = np.random.default_rng(seed)
+    xy_un = np.asarray(xy_un, np.float64).reshape(-1, 2)
+    octave = np.asarray(kps["octave"], np.int64)
+    kangle = np.asarray(kps["angle"], np.float64)
+    desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    nk = len(octave)
+    out = np.zeros(n, RELOC_POINT_DTYPE)
+    if nk == 0 or n == 0:
+        return out
+    fx, fy, cx, cy = (float(v) for v in K)
+    Rcw = np.asarray(pose[0], np.float64).reshape(3, 3)
+    tcw = np.asarray(pose[1], np.float64).reshape(3)
+    scale = scale_factor ** np.arange(nlevels, dtype=np.float64)
+    npool = max(1, min(nk, n // 2 if pool is None else int(pool)))
+    k = rng.choice(nk, size=npool, replace=False)[rng.integers(0, npool, n)]
+    level = np.clip(octave[k] + rng.choice(list(level_offsets), n), 0, nlevels - 1)
+    radius = th * scale[level]
+    uv = xy_un[k] + np.clip(rng.normal(0.0, 0.2, (n, 2)), -0.8, 0.8) * radius[:, None]
+    z = rng.uniform(1.0, 20.0, n)
+    side = np.flatnonzero(rng.random(n) < outside)
+    far = rng.uniform(50.0, 300.0, len(side))
+    for j, (i, d) in enumerate(zip(side, far)):  # every side in turn
+        if j % 4 == 0:
+            uv[i, 0] = bounds[0] - d
+        elif j % 4 == 1:
+            uv[i, 0] = bounds[1] + d
+        elif j % 4 == 2:
+            uv[i, 1] = bounds[2] - d
+        else:
+            uv[i, 1] = bounds[3] + d
+    pc = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    pw = (pc - tcw) @ Rcw  # Rcw^T (pc - tcw)
+    dist = np.linalg.norm(pc, axis=1)  # |X - Ow|
+    ratio = np.where(level == 0, rng.uniform(0.86, 0.99, n), scale_factor ** (level - 0.5))
+    ratio = np.where(rng.random(n) < over_top, scale_factor ** (nlevels - 1) * 1.1, ratio)
+    maxd = dist * ratio
+    mind = maxd / scale_factor ** (nlevels - 1)
+    near = rng.random(n) < too_near
+    mind = np.where(near, dist * 1.3, mind)
+    maxd = np.where(rng.random(n) < too_far, dist / 1.3, maxd)
+    bad = np.flatnonzero(rng.random(n) < not_finite)
+    for j, i in enumerate(bad):  # every kind in turn
+        if j % 3 == 0:
+            pw[i, j % 2] = np.nan
+        elif j % 3 == 1:
+            pw[i] = pw[i] / np.linalg.norm(pw[i]) * 1e30
+            maxd[i], mind[i] = np.inf, 0.0
+        else:
+            maxd[i] = np.inf
+    out["pos"] = pw.astype(np.float32)
+    out["min_distance"] = mind.astype(np.float32)
+    out["max_distance"] = maxd.astype(np.float32)
+    ang = np.mod(kangle[k] + 20.0 + rng.normal(0.0, 3.0, n), 360.0)
+    ang = np.where(rng.random(n) < 0.10, rng.uniform(0.0, 360.0, n), ang)
+    ang = ang + np.where(rng.random(n) < wild_angles, rng.choice([-720.0, 720.0], n), 0.0)
+    out["angle"] = ang.astype(np.float32)
+    out["flags"] = np.where(rng.random(n) < 1.0 - invalid, RP_VALID, 0)
+    d = desc[k].copy()
+    nflip = rng.choice(list(flips), n)
+    for i in range(n):
+        if nflip[i]:
+            b = np.unpackbits(d[i])
+            b[rng.choice(256, nflip[i], replace=False)] ^= 1
+            d[i] = np.packbits(b)
+    out["desc"] = d
+    return out
