@@ -669,24 +669,54 @@ class BatchExtractor:
         return tuple(a[:n.value] for a in r)
 
     @staticmethod
-    def _map_point_rows(map_points, dtype=MAP_POINT_DTYPE):
+    def _map_point_rows(map_points, dtype=MAP_POINT_DTYPE, n=None):
         """(points, offsets, n_frames) for the C ABI: map_points is either a list (one per frame)
         of `dtype` arrays (MAP_POINT_DTYPE; LAST_POINT_DTYPE for track_by_projection), concatenated
         here, or a tuple (points, offsets) already in the ABI's form -- every frame's points in one
-        array and int32 offsets [n + 1] -- which is passed through without a host copy."""
+        array and int32 offsets [n + 1] -- which is passed through without a host copy.  n: the
+        searches over pairs give their pair count; their offsets need only lie inside the points."""
         if isinstance(map_points, tuple):
             mps, off = map_points
-            mps = np.ascontiguousarray(mps, dtype)
+            mps = np.ascontiguousarray(mps, dtype).reshape(-1)
             off = np.ascontiguousarray(off, np.int32)
-            if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(mps) or np.any(np.diff(off) < 0):
-                raise ValueError("map point offsets must start at 0, not decrease and end at len(points)")
+            if n is None:
+                if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(mps) or np.any(np.diff(off) < 0):
+                    raise ValueError("map point offsets must start at 0, not decrease and end at len(points)")
+            elif off.ndim != 1 or len(off) != n + 1 or off.min() < 0 or off.max() > len(mps):
+                raise ValueError("keyframe offsets: one entry per pair plus one, inside the points")
             return mps, off, len(off) - 1
-        nf = len(map_points)
-        mps = np.ascontiguousarray(np.concatenate([np.asarray(m, dtype) for m in map_points])
-                                   if nf else np.zeros(0, dtype))
-        off = np.zeros(nf + 1, np.int32)
-        off[1:] = np.cumsum([len(m) for m in map_points])
-        return mps, off, nf
+        if n is not None and len(map_points) != n:
+            raise ValueError("one array of keyframe points per pair")
+        rows = [np.asarray(m, dtype).reshape(-1) for m in map_points]
+        mps = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, dtype))
+        off = np.zeros(len(rows) + 1, np.int32)
+        off[1:] = np.cumsum([len(m) for m in rows])
+        return mps, off, len(rows)
+
+    @staticmethod
+    def _pad_rows(rows, dtype, fill, n=None, inner=()):
+        """(array [n, stride, *inner], stride) of `fill`-padded rows for the C ABI, (None, 0) for None:
+        rows is a list of 1-D (inner == (2,): [k, 2]) rows, n of them (None: len(rows)), or one array
+        that is padded already, which is passed through."""
+        if rows is None:
+            return None, 0
+        if isinstance(rows, np.ndarray) and rows.ndim == 2 + len(inner) and (
+                n is None or (rows.shape[0] == n and rows.shape[1] > 0)):
+            out = np.ascontiguousarray(rows, dtype)
+        else:
+            rows = [np.asarray(r, dtype).reshape((-1,) + inner) for r in rows]
+            out = np.full((len(rows) if n is None else n, max([1] + [len(r) for r in rows])) + inner, fill, dtype)
+            for p, r in enumerate(rows):
+                out[p, :len(r)] = r
+        return out, out.shape[1]
+
+    def _download_matches(self, fn, row, cap):
+        """(match [n_kp] int32, nmatches, rot_hist [30] int32) of result row `row` through fn."""
+        m = np.zeros(cap, np.int32)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(fn(self.ctx.handle, row, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
+        return m[:n.value], nm.value, h
 
     def search_by_projection(self, map_points, image_step=2, use_uright=True, kp_block=None, th=1.0,
                              nnratio=0.8, far_points=False, th_far=50.0, stream=None):
@@ -696,12 +726,7 @@ class BatchExtractor:
         frame's points in one array (_map_point_rows); kp_block: optional list of u8 arrays (1 =
         keypoint already holds a map point with observations)."""
         mps, off, nf = self._map_point_rows(map_points)
-        blk, stride = None, 0
-        if kp_block is not None:
-            stride = max(1, max(len(b) for b in kp_block))
-            blk = np.zeros((nf, stride), np.uint8)
-            for f, b in enumerate(kp_block):
-                blk[f, :len(b)] = b
+        blk, stride = self._pad_rows(kp_block, np.uint8, 0, nf)
         _check(_lib.orbgpu_search_by_projection_batch(
             self.ctx.handle, nf, int(image_step), int(use_uright), _p(mps) if len(mps) else None, _p(off),
             _p(blk) if blk is not None else None, stride, C.c_float(th), C.c_float(nnratio),
@@ -714,24 +739,15 @@ class BatchExtractor:
         per pair int32 arrays (mvLeftToRightMatch / mvRightToLeftMatch); kp_block per pair over
         Nleft + Nright keypoints; map_points as for search_by_projection."""
         mps, off, nf = self._map_point_rows(map_points)
-
-        def rows(lst, dtype, fill):
-            if lst is None:
-                return None, 0
-            stride = max(1, max(len(x) for x in lst))
-            out = np.full((nf, stride), fill, dtype)
-            for f, x in enumerate(lst):
-                out[f, :len(x)] = x
-            return out, stride
-        l2r, lrs = rows(left_to_right, np.int32, -1)
-        r2l, lrs2 = rows(right_to_left, np.int32, -1)
+        l2r, lrs = self._pad_rows(left_to_right, np.int32, -1, nf)
+        r2l, lrs2 = self._pad_rows(right_to_left, np.int32, -1, nf)
         if l2r is not None and r2l is not None and lrs != lrs2:
             w = max(lrs, lrs2)
             l2r = np.pad(l2r, ((0, 0), (0, w - lrs)), constant_values=-1)
             r2l = np.pad(r2l, ((0, 0), (0, w - lrs2)), constant_values=-1)
             lrs = w
         lrs = lrs or lrs2
-        blk, bst = rows(kp_block, np.uint8, 0)
+        blk, bst = self._pad_rows(kp_block, np.uint8, 0, nf)
         _check(_lib.orbgpu_search_by_projection_stereo(
             self.ctx.handle, nf, _p(mps) if len(mps) else None, _p(off),
             _p(l2r) if l2r is not None else None, _p(r2l) if r2l is not None else None, lrs,
@@ -758,12 +774,7 @@ class BatchExtractor:
         if len(ps) != nf:
             raise ValueError("one pose per frame")
         Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
-        blk, stride = None, 0
-        if kp_block is not None:
-            stride = max(1, max(len(b) for b in kp_block))
-            blk = np.zeros((nf, stride), np.uint8)
-            for f, b in enumerate(kp_block):
-                blk[f, :len(b)] = b
+        blk, stride = self._pad_rows(kp_block, np.uint8, 0, nf)
         _check(_lib.orbgpu_track_by_projection_batch(
             self.ctx.handle, nf, int(image_step), int(use_uright), _p(pts) if len(pts) else None, _p(off), _p(ps),
             _p(Kf), C.c_float(mbf), C.c_float(mb), _p(blk) if blk is not None else None, stride, C.c_float(th),
@@ -785,12 +796,7 @@ class BatchExtractor:
             rg = np.ascontiguousarray(rig, TRACK_RIG_DTYPE).reshape(-1)
             if len(rg) != 1:
                 raise ValueError("one rig")
-        blk, stride = None, 0
-        if kp_block is not None:
-            stride = max(1, max(len(b) for b in kp_block))
-            blk = np.zeros((nf, stride), np.uint8)
-            for f, b in enumerate(kp_block):
-                blk[f, :len(b)] = b
+        blk, stride = self._pad_rows(kp_block, np.uint8, 0, nf)
         _check(_lib.orbgpu_track_by_projection_stereo(
             self.ctx.handle, nf, _p(pts) if len(pts) else None, _p(off), _p(ps), _p(rg) if rg is not None else None,
             C.c_float(mb), _p(blk) if blk is not None else None, stride, C.c_float(th), int(mono),
@@ -800,11 +806,7 @@ class BatchExtractor:
         """(match [n_kp] int32: last-frame point index or -1, nmatches, rot_hist [30] int32: the bin
         sizes before the three-maxima rule) of frame `frame`; n_kp = Nleft + Nright after
         track_by_projection_stereo."""
-        m = np.zeros(cap, np.int32)
-        h = np.zeros(30, np.int32)
-        n, nm = C.c_int(0), C.c_int(0)
-        _check(_lib.orbgpu_download_track_matches(self.ctx.handle, frame, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
-        return m[:n.value], nm.value, h
+        return self._download_matches(_lib.orbgpu_download_track_matches, frame, cap)
 
     def search_for_initialization(self, image_pairs, prev_matched=None, window_size=100, nnratio=0.9,
                                   check_orientation=True, stream=None):
@@ -813,18 +815,9 @@ class BatchExtractor:
         (F1, F2) of batch images after undistort_grid(); prev_matched: a list (one per pair) of
         [n1, 2] float32 arrays, or one padded [n_pairs, stride, 2] array; None: F1's mvKeysUn.pt."""
         pairs = np.ascontiguousarray(image_pairs, np.int32).reshape(-1, 2)
-        pm, stride = None, 0
-        if prev_matched is not None:
-            if isinstance(prev_matched, np.ndarray) and prev_matched.ndim == 3:
-                pm = np.ascontiguousarray(prev_matched, np.float32)
-            else:
-                rows = [np.asarray(r, np.float32).reshape(-1, 2) for r in prev_matched]
-                pm = np.zeros((len(rows), max([1] + [len(r) for r in rows]), 2), np.float32)
-                for p, r in enumerate(rows):
-                    pm[p, :len(r)] = r
-            if pm.shape[0] != len(pairs) or pm.shape[2] != 2:
-                raise ValueError("one row of [n1, 2] points per pair")
-            stride = pm.shape[1]
+        pm, stride = self._pad_rows(prev_matched, np.float32, 0, inner=(2,))
+        if pm is not None and (pm.shape[0] != len(pairs) or pm.shape[2] != 2):
+            raise ValueError("one row of [n1, 2] points per pair")
         _check(_lib.orbgpu_search_for_initialization_batch(
             self.ctx.handle, len(pairs), _p(pairs) if len(pairs) else None, _p(pm) if pm is not None else None,
             stride, int(window_size), C.c_float(nnratio), int(check_orientation),
@@ -852,26 +845,8 @@ class BatchExtractor:
         [n_pairs, stride]."""
         fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
         npairs = len(fr)
-        if isinstance(kf_points, tuple):
-            pts, off = kf_points
-            pts = np.ascontiguousarray(pts, BOW_POINT_DTYPE).reshape(-1)
-            off = np.ascontiguousarray(off, np.int32)
-            if off.ndim != 1 or len(off) != npairs + 1 or off.min() < 0 or off.max() > len(pts):
-                raise ValueError("keyframe offsets: one entry per pair plus one, inside the points")
-        else:
-            if len(kf_points) != npairs:
-                raise ValueError("one array of keyframe points per pair")
-            rows = [np.asarray(r, BOW_POINT_DTYPE).reshape(-1) for r in kf_points]
-            pts = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, BOW_POINT_DTYPE))
-            off = np.zeros(npairs + 1, np.int32)
-            off[1:] = np.cumsum([len(r) for r in rows])
-        if isinstance(f_nodes, np.ndarray) and f_nodes.ndim == 2:
-            nodes = np.ascontiguousarray(f_nodes, np.int32)
-        else:
-            rows = [np.asarray(r, np.int32).reshape(-1) for r in f_nodes]
-            nodes = np.full((len(rows), max([1] + [len(r) for r in rows])), -1, np.int32)
-            for p, r in enumerate(rows):
-                nodes[p, :len(r)] = r
+        pts, off, _ = self._map_point_rows(kf_points, BOW_POINT_DTYPE, npairs)
+        nodes, _ = self._pad_rows(f_nodes, np.int32, -1)
         if nodes.shape[0] != npairs:
             raise ValueError("one row of nodes per pair")
         _check(_lib.orbgpu_search_by_bow_batch(
@@ -883,11 +858,7 @@ class BatchExtractor:
         """(match [N] int32: for each keypoint of F the index, within the pair's keyframe points, of
         the point that ends up in vpMapPointMatches, -1 if none; nmatches; rot_hist [30] int32: the
         bin sizes before the three-maxima rule) of pair `pair` of the last search_by_bow."""
-        m = np.zeros(cap, np.int32)
-        h = np.zeros(30, np.int32)
-        n, nm = C.c_int(0), C.c_int(0)
-        _check(_lib.orbgpu_download_bow_matches(self.ctx.handle, pair, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
-        return m[:n.value], nm.value, h
+        return self._download_matches(_lib.orbgpu_download_bow_matches, pair, cap)
 
     def reloc_by_projection(self, frames, kf_points, poses, K, kp_block=None, th=10.0, orb_dist=100,
                             check_orientation=True, stream=None):
@@ -900,35 +871,14 @@ class BatchExtractor:
         arrays, or one 2-D array (non-zero = the keypoint already holds a map point)."""
         fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
         npairs = len(fr)
-        if isinstance(kf_points, tuple):
-            pts, off = kf_points
-            pts = np.ascontiguousarray(pts, RELOC_POINT_DTYPE).reshape(-1)
-            off = np.ascontiguousarray(off, np.int32)
-            if off.ndim != 1 or len(off) != npairs + 1 or off.min() < 0 or off.max() > len(pts):
-                raise ValueError("keyframe offsets: one entry per pair plus one, inside the points")
-        else:
-            if len(kf_points) != npairs:
-                raise ValueError("one array of keyframe points per pair")
-            rows = [np.asarray(r, RELOC_POINT_DTYPE).reshape(-1) for r in kf_points]
-            pts = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, RELOC_POINT_DTYPE))
-            off = np.zeros(npairs + 1, np.int32)
-            off[1:] = np.cumsum([len(r) for r in rows])
+        pts, off, _ = self._map_point_rows(kf_points, RELOC_POINT_DTYPE, npairs)
         ps = np.ascontiguousarray(poses, RELOC_POSE_DTYPE).reshape(-1)
         if len(ps) != npairs:
             raise ValueError("one pose per pair")
         Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
-        blk, stride = None, 0
-        if kp_block is not None:
-            if isinstance(kp_block, np.ndarray) and kp_block.ndim == 2:
-                blk = np.ascontiguousarray(kp_block, np.uint8)
-            else:
-                rows = [np.asarray(b, np.uint8).reshape(-1) for b in kp_block]
-                blk = np.zeros((len(rows), max([1] + [len(b) for b in rows])), np.uint8)
-                for p, b in enumerate(rows):
-                    blk[p, :len(b)] = b
-            if blk.shape[0] != npairs:
-                raise ValueError("one row of occupancy per pair")
-            stride = blk.shape[1]
+        blk, stride = self._pad_rows(kp_block, np.uint8, 0)
+        if blk is not None and blk.shape[0] != npairs:
+            raise ValueError("one row of occupancy per pair")
         _check(_lib.orbgpu_reloc_by_projection_batch(
             self.ctx.handle, npairs, _p(fr) if npairs else None, _p(pts) if len(pts) else None,
             _p(off) if npairs else None, _p(ps) if npairs else None, _p(Kf),
@@ -940,11 +890,7 @@ class BatchExtractor:
         points, of the point this call put into mvpMapPoints, -1 if none; nmatches; rot_hist [30]
         int32: the bin sizes before the three-maxima rule) of pair `pair` of the last
         reloc_by_projection."""
-        m = np.zeros(cap, np.int32)
-        h = np.zeros(30, np.int32)
-        n, nm = C.c_int(0), C.c_int(0)
-        _check(_lib.orbgpu_download_reloc_matches(self.ctx.handle, pair, _p(m), cap, C.byref(n), C.byref(nm), _p(h)))
-        return m[:n.value], nm.value, h
+        return self._download_matches(_lib.orbgpu_download_reloc_matches, pair, cap)
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

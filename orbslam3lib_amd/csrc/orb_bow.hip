@@ -47,7 +47,6 @@ namespace {
 constexpr int kThLow = 50;  // ORBmatcher::TH_LOW
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr uint64_t kNoNode = ~0ull;  // sorts behind every node id
-constexpr int kNoBin = 31;           // an event outside [0, 30), or no orientation check
 constexpr int kGroupThreads = 1024;
 constexpr int kMatchWaves = 128;     // waves per pair in k_bow_match, each striding over the segments (measured:
                                      // 16 / 32 / 64 / 128 -> 0.228 / 0.218 / 0.208 / 0.199 ms per 256 pairs)
@@ -152,15 +151,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_bow_group(BowArgs a) {
 __device__ inline void bow_commit(const BowArgs& a, int32_t* match, uint8_t* mbin, int idxF, float angF, int kidx,
                                   float kang) {
     uint32_t bin = kNoBin;
-    if (a.check_orientation) {
-        float rot = kang - angF;
-        if (rot < 0.0f) rot += 360.0f;
-        const float rb = roundf(rot * (1.0f / 30));
-        if (rb >= 0.f && rb <= 30.f) {
-            bin = (uint32_t)(int)rb;
-            if (bin == kRotBins) bin = 0;
-        }
-    }
+    if (a.check_orientation) rot_bin(kang, angF, &bin);
     match[idxF] = kidx;
     mbin[idxF] = (uint8_t)bin;
 }

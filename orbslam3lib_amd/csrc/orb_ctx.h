@@ -1,6 +1,6 @@
 // orb_ctx.h -- internal to liborbgpu.so: the context (orbgpu_ctx), its device buffers, the error
 // and stream helpers and the two dispatch helpers shared by orb_runtime.cpp (create, ingest, the
-// batch itself) and orb_post.cpp (everything that runs after a batch).
+// batch itself), orb_post.cpp (what runs after a batch) and orb_matchers.cpp (the ORBmatcher searches).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -99,6 +99,9 @@ struct DiagKnobs {
     bool fast_ovf_all = false;  // ORBGPU_FAST_OVF_ALL: every small-list cell through the overflow pass
 };
 
+// What a matcher's last call left on the device: result row r is over batch image image[r] (two_cam: and image[r] + 1).
+struct MatchCover { std::vector<int32_t> image; bool two_cam = false; };
+
 // Device-to-host copy on the context's own stream, waited for before the call returns (the
 // callers ran ctx_sync first, so the stream is idle and the copy sees every result).  Never a
 // null-stream hipMemcpy: that would also order against other contexts' and torch's work.
@@ -136,11 +139,8 @@ struct orbgpu_ctx {
         bowgrp{bufs}, bowdesc{bufs}, bowmatch{bufs}, bownm{bufs}, relin{bufs}, relpt{bufs}, relpose{bufs},
         relcand{bufs}, relblk{bufs}, relmatch{bufs}, relnm{bufs};
     float grid_bounds[4] = {0, 0, 0, 0}, grid_inv[2] = {0, 0};  // of the last undistort_grid
-    int sbp_frames = 0, sbp_step = 1, sbp_two_cam = 0;
-    int trk_frames = 0, trk_step = 1, trk_two_cam = 0;  // coverage of the last orbgpu_track_by_projection_*
-    std::vector<int32_t> init_pairs;  // {F1, F2} of the last orbgpu_search_for_initialization_batch
-    std::vector<int32_t> bow_frames;  // F of each pair of the last orbgpu_search_by_bow_batch
-    std::vector<int32_t> reloc_frames;  // CurrentFrame of each pair of the last orbgpu_reloc_by_projection_batch
+    // coverage of the last call of each ORBmatcher search (orb_matchers.cpp; init_cover: F1 of each pair)
+    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover;
     int soa_images = 0, soa_pairs = 0;  // coverage of the last orbgpu_pack_soa
     int grid_images = 0;   // images of the last orbgpu_undistort_grid_batch
     int stereo_pairs = 0;  // pairs of the last orbgpu_stereo_matches_batch

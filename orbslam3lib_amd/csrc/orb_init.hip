@@ -56,7 +56,6 @@ namespace {
 constexpr int kThLow = 50;         // ORBmatcher::TH_LOW
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr uint32_t kNoDist = 0xFFFFu;  // vMatchedDistance's INT_MAX
-constexpr int kNoBin = 31;         // an event outside [0, 30)
 
 // vbPrevMatched of the pair (the caller's, or F1's mvKeysUn.pt).
 __device__ inline const float* init_prev(const InitArgs& a, int pair, const FrameView& F1) {
@@ -334,14 +333,7 @@ __global__ __launch_bounds__(64) void k_init_replay(InitArgs a) {
                 md[b] = (uint32_t)bd;
                 uint32_t bin = kNoBin;
                 if (a.check_orientation) {
-                    float rot = angle_of(F1, c.i1) - angle_of(F2, b);
-                    if (rot < 0.0f) rot += 360.0f;
-                    const float rb = roundf(rot * (1.0f / 30));
-                    if (rb >= 0.f && rb <= 30.f) {
-                        bin = (uint32_t)(int)rb;
-                        if (bin == kRotBins) bin = 0;
-                        atomicAdd(&hist[bin], 1u);
-                    }
+                    if (rot_bin(angle_of(F1, c.i1), angle_of(F2, b), &bin)) atomicAdd(&hist[bin], 1u);
                 }
                 obin[b] = bin;
             }

@@ -1,5 +1,5 @@
 // orb_kernels.h -- launch-argument structs shared by the kernel files and the host runtime
-// (orb_geometry.h fills them, orb_runtime.cpp and orb_post.cpp bind the pointers and launch).
+// (orb_geometry.h fills them, orb_runtime.cpp, orb_post.cpp and orb_matchers.cpp bind the pointers and launch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,6 +1,7 @@
 // orb_post.cpp -- the part of the C ABI (include/orbgpu.h) that runs after a batch: matching,
-// stereo, fisheye, grid and SearchByProjection over the device-resident results, SoA packing and
-// export, and every download / getter.  The context and the dispatch helpers are in orb_ctx.h.
+// stereo, fisheye and grid over the device-resident results, SoA packing and export, and their
+// downloads / getters.  The ORBmatcher searches are in orb_matchers.cpp; the context and the
+// dispatch helpers are in orb_ctx.h.
 #include <cstdio>
 #include <cstdlib>
 
@@ -526,644 +527,6 @@ int orbgpu_download_matches16(orbgpu_ctx* c, int pair, int16_t* indices, int16_t
     int16_t* dst[3] = {indices, dist1, dist2};
     for (int k = 0; k < 3; ++k)
         if (dst[k]) D2H(dst[k], c->m16.as<int16_t>() + k * mplane + o, 2 * (size_t)n);
-    return ORBGPU_OK;
-}
-
-namespace {
-
-// Shared by the pinhole and two-camera entry points (orb_sbp.hip).
-int sbp_run(orbgpu_ctx* c, int n_frames, int image_step, int two_cam, int use_uright,
-            const orbgpu_map_point* mps, const int32_t* mp_offsets, const int32_t* l2r, const int32_t* r2l,
-            int lr_stride, const uint8_t* kp_block, int kp_stride, float th, float nnratio, int far_points,
-            float th_far, void* stream) {
-    static_assert(sizeof(orbgpu_map_point) == sizeof(MapPointIn), "map point layout");
-    if (!c || !mp_offsets || n_frames < 1) return fail(ORBGPU_ERR_INVALID, "null argument");
-    const int images_needed = (n_frames - 1) * image_step + (two_cam ? 2 : 1);
-    if (image_step < 1 || images_needed > c->grid_images)
-        return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
-    if (use_uright && (image_step != 2 || n_frames > c->stereo_pairs))
-        return fail(ORBGPU_ERR_INVALID, "mvuRight needs image_step 2 and a stereo_matches_batch over the pairs");
-    if (sbp_resolve_lds_bytes(c->plan.out_cap, two_cam) > 160 * 1024)
-        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if ((kp_block && kp_stride < 1) || ((l2r || r2l) && lr_stride < 1))
-        return fail(ORBGPU_ERR_INVALID, "stride");
-    const int total = mp_offsets[n_frames];
-    int max_mps = 0;
-    for (int f = 0; f < n_frames; ++f) {
-        if (mp_offsets[f + 1] < mp_offsets[f] || mp_offsets[0] != 0) return fail(ORBGPU_ERR_INVALID, "mp_offsets");
-        max_mps = std::max(max_mps, mp_offsets[f + 1] - mp_offsets[f]);
-    }
-    if (total > 0 && !mps) return fail(ORBGPU_ERR_INVALID, "null map points");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = (size_t)c->plan.out_cap, ncap = two_cam ? 2 * cap : cap;
-    if (c->sbpmp.ensure((size_t)total * sizeof(MapPointIn) + 256) ||
-        c->sbpoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
-        c->sbpcand.ensure((size_t)total * sizeof(SbpCand) + 256) ||
-        c->sbpmatch.ensure((size_t)n_frames * ncap * 4 + 256) || c->sbpnm.ensure((size_t)n_frames * 4 + 256) ||
-        (kp_block && c->sbpblk.ensure((size_t)n_frames * ncap + 256)) ||
-        ((l2r || r2l) && c->sbplr.ensure((size_t)n_frames * cap * 8 + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (projection search)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int r = join_all(c, s);  // keypoints, grid and mvuRight come from the chunk streams
-    if (r) return r;
-    // host inputs are pageable: copy, then wait so the caller may reuse them on return
-    if (total) HIP_TRY(hipMemcpyAsync(c->sbpmp.p, mps, (size_t)total * sizeof(MapPointIn), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->sbpoff.p, mp_offsets, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    if (kp_block) {
-        HIP_TRY(hipMemsetAsync(c->sbpblk.p, 0, (size_t)n_frames * ncap, s));
-        HIP_TRY(hipMemcpy2DAsync(c->sbpblk.p, ncap, kp_block, kp_stride, std::min((size_t)kp_stride, ncap),
-                                 n_frames, hipMemcpyHostToDevice, s));
-    }
-    int32_t* dl2r = c->sbplr.as<int32_t>();
-    int32_t* dr2l = dl2r ? dl2r + (size_t)n_frames * cap : nullptr;
-    const size_t lrw = std::min((size_t)lr_stride, cap) * 4;
-    if (l2r) {
-        HIP_TRY(hipMemsetAsync(dl2r, 0xFF, (size_t)n_frames * cap * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(dl2r, cap * 4, l2r, (size_t)lr_stride * 4, lrw, n_frames, hipMemcpyHostToDevice, s));
-    }
-    if (r2l) {
-        HIP_TRY(hipMemsetAsync(dr2l, 0xFF, (size_t)n_frames * cap * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(dr2l, cap * 4, r2l, (size_t)lr_stride * 4, lrw, n_frames, hipMemcpyHostToDevice, s));
-    }
-    SbpArgs a{};
-    a.mps = c->sbpmp.as<MapPointIn>();
-    a.mp_off = c->sbpoff.as<int32_t>();
-    a.cand = c->sbpcand.as<SbpCand>();
-    a.kps = c->outkps.p;
-    a.out_n = c->outn.as<int32_t>();
-    a.out_cap = c->plan.out_cap;
-    a.xy_un = c->gxy.as<float>();
-    a.cell_start = c->gstart.as<int32_t>();
-    a.cell_idx = c->gidx.as<int32_t>();
-    a.desc = c->outdesc.as<uint8_t>();
-    a.uright = use_uright ? c->stur.as<float>() : nullptr;
-    a.kp_block = kp_block ? c->sbpblk.as<uint8_t>() : nullptr;
-    a.l2r = l2r ? dl2r : nullptr;
-    a.r2l = r2l ? dr2l : nullptr;
-    a.two_cam = two_cam;
-    a.image_step = image_step;
-    a.img0 = 0;
-    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
-    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
-    for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
-    a.nlevels = c->prm.nlevels;
-    a.th = th;
-    a.nnratio = nnratio;
-    a.th_far = th_far;
-    a.far_points = far_points != 0;
-    a.factor = th != 1.0;  // bFactor (:48)
-    a.match = c->sbpmatch.as<int32_t>();
-    a.nmatches = c->sbpnm.as<int32_t>();
-    r = timed(c, ST_SBP, s, [&] { return launch_sbp(a, n_frames, max_mps, s); });
-    if (r) return r;
-    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
-    c->sbp_frames = n_frames;
-    c->sbp_step = image_step;
-    c->sbp_two_cam = two_cam;
-    c->need_fork = true;
-    return ORBGPU_OK;
-}
-
-}  // namespace
-
-int orbgpu_search_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step, int use_uright,
-                                      const orbgpu_map_point* mps, const int32_t* mp_offsets,
-                                      const uint8_t* kp_block, int kp_stride, float th, float nnratio,
-                                      int far_points, float th_far, void* stream) {
-    return sbp_run(c, n_frames, image_step, 0, use_uright, mps, mp_offsets, nullptr, nullptr, 0, kp_block,
-                   kp_stride, th, nnratio, far_points, th_far, stream);
-}
-
-int orbgpu_search_by_projection_stereo(orbgpu_ctx* c, int n_pairs, const orbgpu_map_point* mps,
-                                       const int32_t* mp_offsets, const int32_t* left_to_right,
-                                       const int32_t* right_to_left, int lr_stride, const uint8_t* kp_block,
-                                       int kp_stride, float th, float nnratio, int far_points, float th_far,
-                                       void* stream) {
-    return sbp_run(c, n_pairs, 2, 1, 0, mps, mp_offsets, left_to_right, right_to_left, lr_stride, kp_block,
-                   kp_stride, th, nnratio, far_points, th_far, stream);
-}
-
-int orbgpu_download_projection_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp,
-                                       int* nmatches) {
-    if (!c || frame < 0 || frame >= c->sbp_frames) return fail(ORBGPU_ERR_INVALID, "bad frame");
-    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    int32_t nk[2] = {0, 0}, nm = 0;
-    const size_t img = (size_t)frame * c->sbp_step;
-    D2H(nk, c->outn.as<int32_t>() + img, c->sbp_two_cam ? 8 : 4);
-    D2H(&nm, c->sbpnm.as<int32_t>() + frame, 4);
-    if (int e = count_status(nk[0])) return e;
-    if (c->sbp_two_cam)
-        if (int e = count_status(nk[1])) return e;
-    if (!c->sbp_two_cam) nk[1] = 0;
-    const int n = nk[0] + nk[1];
-    if (n_kp) *n_kp = n;
-    if (nmatches) *nmatches = nm;
-    if (n > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    const size_t ncap = c->sbp_two_cam ? 2 * (size_t)c->plan.out_cap : (size_t)c->plan.out_cap;
-    if (match && n)
-        D2H(match, c->sbpmatch.as<int32_t>() + (size_t)frame * ncap, 4 * (size_t)n);
-    return ORBGPU_OK;
-}
-
-// ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (orb_track.hip) --------
-namespace {
-
-// Shared by the pinhole entry point (K, rig == nullptr) and the two-camera one (rig, K == nullptr:
-// frame f = images 2f and 2f + 1; kp_block and the match array cover Nleft + Nright keypoints).
-int track_run(orbgpu_ctx* c, int n_frames, int image_step, int use_uright, const orbgpu_last_point* pts,
-              const int32_t* pt_offsets, const orbgpu_track_pose* poses, const float* K,
-              const orbgpu_track_rig* rig, float mbf, float mb, const uint8_t* kp_block, int kp_stride, float th,
-              int mono, int check_orientation, void* stream) {
-    static_assert(sizeof(orbgpu_last_point) == sizeof(LastPointIn) && sizeof(orbgpu_last_point) == 56,
-                  "last point layout");
-    static_assert(sizeof(orbgpu_track_pose) == 96, "track pose layout");
-    static_assert(sizeof(orbgpu_track_rig) == sizeof(TrackRig) && sizeof(orbgpu_track_rig) == 80, "track rig layout");
-    const bool two_cam = rig != nullptr;
-    if (!c || !pt_offsets || !poses || (!K && !rig) || n_frames < 1) return fail(ORBGPU_ERR_INVALID, "null argument");
-    if (image_step != 1 && image_step != 2) return fail(ORBGPU_ERR_INVALID, "image_step must be 1 or 2");
-    if ((n_frames - 1) * image_step + (two_cam ? 2 : 1) > c->grid_images)
-        return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
-    if (use_uright && (image_step != 2 || n_frames > c->stereo_pairs))
-        return fail(ORBGPU_ERR_INVALID, "mvuRight needs image_step 2 and a stereo_matches_batch over the pairs");
-    if (track_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
-        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if (kp_block && kp_stride < 1) return fail(ORBGPU_ERR_INVALID, "stride");
-    int max_pts = 0;
-    for (int f = 0; f < n_frames; ++f) {
-        if (pt_offsets[f + 1] < pt_offsets[f] || pt_offsets[0] != 0) return fail(ORBGPU_ERR_INVALID, "pt_offsets");
-        max_pts = std::max(max_pts, pt_offsets[f + 1] - pt_offsets[f]);
-    }
-    const int total = pt_offsets[n_frames];
-    if (total > 0 && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
-    // the motion direction decides the window's level range (:1727-1734)
-    std::vector<TrackFrame> frames(n_frames);
-    for (int f = 0; f < n_frames; ++f) {
-        const orbgpu_track_pose& P = poses[f];
-        TrackFrame& T = frames[f];
-        std::memcpy(T.Rcw, P.Rcw, sizeof T.Rcw);
-        std::memcpy(T.tcw, P.tcw, sizeof T.tcw);
-        float twc[3];
-        for (int k = 0; k < 3; ++k) twc[k] = -((P.Rcw[k] * P.tcw[0] + P.Rcw[3 + k] * P.tcw[1]) + P.Rcw[6 + k] * P.tcw[2]);
-        const float tlc_z = ((P.Rlw[6] * twc[0] + P.Rlw[7] * twc[1]) + P.Rlw[8] * twc[2]) + P.tlw[2];
-        T.dir = mono ? 0 : tlc_z > mb ? kTrackForward : -tlc_z > mb ? kTrackBackward : 0;
-        T.pad[0] = T.pad[1] = T.pad[2] = 0;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = two_cam ? 2 * (size_t)c->plan.out_cap : (size_t)c->plan.out_cap;
-    const size_t sides = two_cam ? 2 : 1;  // candidate records per point
-    if (c->trkpt.ensure((size_t)total * sizeof(LastPointIn) + 256) || c->trkoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
-        c->trkframe.ensure((size_t)n_frames * sizeof(TrackFrame) + 256) ||
-        c->trkcand.ensure(sides * total * sizeof(TrackCand) + 256) || c->trkmatch.ensure((size_t)n_frames * cap * 4 + 256) ||
-        c->trknm.ensure((size_t)n_frames * (1 + kRotBins) * 4 + 256) ||
-        (kp_block && c->trkblk.ensure((size_t)n_frames * cap + 256)) ||
-        (two_cam && (c->trkmask.ensure((size_t)n_frames * cap * 4 + 256) ||
-                     c->trkside.ensure((size_t)n_frames * 2 * (kRotBins + 1) * 4 + 256))))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (motion-model search)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int r = join_all(c, s);  // keypoints, grid and mvuRight come from the chunk streams
-    if (r) return r;
-    // host inputs are pageable: copy, then wait so the caller may reuse them on return
-    if (total) HIP_TRY(hipMemcpyAsync(c->trkpt.p, pts, (size_t)total * sizeof(LastPointIn), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->trkoff.p, pt_offsets, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->trkframe.p, frames.data(), (size_t)n_frames * sizeof(TrackFrame), hipMemcpyHostToDevice, s));
-    if (kp_block) {
-        HIP_TRY(hipMemsetAsync(c->trkblk.p, 0, (size_t)n_frames * cap, s));
-        HIP_TRY(hipMemcpy2DAsync(c->trkblk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), n_frames,
-                                 hipMemcpyHostToDevice, s));
-    }
-    TrackStereoArgs a{};
-    a.pts = c->trkpt.as<LastPointIn>();
-    a.pt_off = c->trkoff.as<int32_t>();
-    a.frames = c->trkframe.as<TrackFrame>();
-    a.cand = c->trkcand.as<TrackCand>();
-    a.kps = c->outkps.p;
-    a.out_n = c->outn.as<int32_t>();
-    a.out_cap = c->plan.out_cap;
-    a.xy_un = c->gxy.as<float>();
-    a.cell_start = c->gstart.as<int32_t>();
-    a.cell_idx = c->gidx.as<int32_t>();
-    a.desc = c->outdesc.as<uint8_t>();
-    a.uright = use_uright ? c->stur.as<float>() : nullptr;
-    a.kp_block = kp_block ? c->trkblk.as<uint8_t>() : nullptr;
-    a.image_step = image_step;
-    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
-    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
-    for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
-    a.nlevels = c->prm.nlevels;
-    for (int k = 0; k < 4; ++k) a.K[k] = K ? K[k] : 0.f;
-    a.mbf = mbf;
-    a.th = th;
-    a.check_orientation = check_orientation != 0;
-    a.match = c->trkmatch.as<int32_t>();
-    a.nmatches = c->trknm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_frames;
-    if (two_cam) {
-        std::memcpy(&a.rig, rig, sizeof a.rig);
-        a.side_mask = c->trkmask.as<uint32_t>();
-        a.side_hist = c->trkside.as<int32_t>();
-    }
-    r = timed(c, ST_SBP, s, [&] {
-        return two_cam ? launch_track_stereo(a, n_frames, max_pts, s)
-                       : launch_track(static_cast<const TrackArgs&>(a), n_frames, max_pts, s);
-    });
-    if (r) return r;
-    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
-    c->trk_frames = n_frames;
-    c->trk_step = image_step;
-    c->trk_two_cam = two_cam;
-    c->need_fork = true;
-    return ORBGPU_OK;
-}
-
-}  // namespace
-
-int orbgpu_track_by_projection_batch(orbgpu_ctx* c, int n_frames, int image_step, int use_uright,
-                                     const orbgpu_last_point* pts, const int32_t* pt_offsets,
-                                     const orbgpu_track_pose* poses, const float K[4], float mbf, float mb,
-                                     const uint8_t* kp_block, int kp_stride, float th, int mono,
-                                     int check_orientation, void* stream) {
-    if (!K) return fail(ORBGPU_ERR_INVALID, "null argument");
-    return track_run(c, n_frames, image_step, use_uright, pts, pt_offsets, poses, K, nullptr, mbf, mb, kp_block,
-                     kp_stride, th, mono, check_orientation, stream);
-}
-
-int orbgpu_track_by_projection_stereo(orbgpu_ctx* c, int n_pairs, const orbgpu_last_point* pts,
-                                      const int32_t* pt_offsets, const orbgpu_track_pose* poses,
-                                      const orbgpu_track_rig* rig, float mb, const uint8_t* kp_block, int kp_stride,
-                                      float th, int mono, int check_orientation, void* stream) {
-    if (!rig) return fail(ORBGPU_ERR_INVALID, "null argument");
-    return track_run(c, n_pairs, 2, 0, pts, pt_offsets, poses, nullptr, rig, 0.f, mb, kp_block, kp_stride, th, mono,
-                     check_orientation, stream);
-}
-
-int orbgpu_download_track_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp, int* nmatches,
-                                  int32_t rot_hist[30]) {
-    if (!c || frame < 0 || frame >= c->trk_frames) return fail(ORBGPU_ERR_INVALID, "bad frame");
-    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    int32_t nks[2] = {0, 0}, nm = 0;
-    D2H(nks, c->outn.as<int32_t>() + (size_t)frame * c->trk_step, c->trk_two_cam ? 8 : 4);
-    D2H(&nm, c->trknm.as<int32_t>() + frame, 4);
-    if (int e = count_status(nks[0])) return e;
-    if (c->trk_two_cam)
-        if (int e = count_status(nks[1])) return e;
-    if (!c->trk_two_cam) nks[1] = 0;
-    const int nk = nks[0] + nks[1];  // two-camera frames: Nleft + Nright, the right ones from Nleft on
-    if (n_kp) *n_kp = nk;
-    if (nmatches) *nmatches = nm;
-    if (rot_hist) D2H(rot_hist, c->trknm.as<int32_t>() + c->trk_frames + (size_t)frame * kRotBins, 4 * kRotBins);
-    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    const size_t ncap = c->trk_two_cam ? 2 * (size_t)c->plan.out_cap : (size_t)c->plan.out_cap;
-    if (match && nk) D2H(match, c->trkmatch.as<int32_t>() + (size_t)frame * ncap, 4 * (size_t)nk);
-    return ORBGPU_OK;
-}
-
-// ---- ORBmatcher::SearchForInitialization (orb_init.hip) -----------------------------------------
-int orbgpu_search_for_initialization_batch(orbgpu_ctx* c, int n_pairs, const int32_t* image_pairs,
-                                           const float* prev_matched, int pm_stride, int window_size, float nnratio,
-                                           int check_orientation, void* stream) {
-    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
-    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
-    if (n_pairs > 0 && !image_pairs) return fail(ORBGPU_ERR_INVALID, "null image pairs");
-    if (window_size < 0) return fail(ORBGPU_ERR_INVALID, "negative window");
-    for (int k = 0; k < 2 * n_pairs; ++k)
-        if (image_pairs[k] < 0 || image_pairs[k] >= c->grid_images)
-            return fail(ORBGPU_ERR_INVALID, "images must lie in the last orbgpu_undistort_grid_batch");
-    if (n_pairs > 0 && init_replay_lds_bytes(c->plan.out_cap) > 160 * 1024)
-        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if (n_pairs == 0) {
-        c->init_pairs.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
-    if (prev_matched) {  // one row of pm_stride points per pair: it must cover F1's keypoints
-        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-        std::vector<int32_t> counts((size_t)c->grid_images);
-        D2H(counts.data(), c->outn.p, counts.size() * 4);
-        for (int p = 0; p < n_pairs; ++p)
-            if (pm_stride < std::min(counts[image_pairs[2 * p]], (int32_t)cap))
-                return fail(ORBGPU_ERR_INVALID, "pm_stride below F1's keypoint count");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->inipair.ensure(np * 12 + 256) || c->inicand.ensure(np * cap * sizeof(InitCand) + 256) ||
-        c->inimatch.ensure(np * cap * 4 + 256) || c->inipout.ensure(np * cap * 8 + 256) ||
-        c->ininm.ensure(np * (1 + kRotBins) * 4 + 256) || c->inil0.ensure(np * (cap + 4) * 48 + 256) ||
-        (prev_matched && c->iniprev.ensure(np * cap * 8 + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (initialization search)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int r = join_all(c, s);  // keypoints and grid come from the chunk streams
-    if (r) return r;
-    // host inputs are pageable: copy, then wait so the caller may reuse them on return
-    int32_t* dpairs = c->inipair.as<int32_t>();
-    HIP_TRY(hipMemcpyAsync(dpairs, image_pairs, np * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(dpairs + 2 * np, 0, np * 4, s));  // the searched-keypoint counts
-    if (prev_matched) {
-        const size_t w = std::min((size_t)pm_stride, cap) * 8;
-        if (w)
-            HIP_TRY(hipMemcpy2DAsync(c->iniprev.p, cap * 8, prev_matched, (size_t)pm_stride * 8, w, np,
-                                     hipMemcpyHostToDevice, s));
-    }
-    InitArgs a{};
-    a.pairs = dpairs;
-    a.prev = prev_matched ? c->iniprev.as<float>() : nullptr;
-    a.cand = c->inicand.as<InitCand>();
-    a.nsearch = dpairs + 2 * np;
-    a.l0_desc = c->inil0.as<uint8_t>();
-    a.l0_xy = reinterpret_cast<float*>(a.l0_desc + np * cap * 32);
-    a.l0_idx = reinterpret_cast<int32_t*>(a.l0_xy + np * cap * 2);
-    a.l0_pre = a.l0_idx + np * cap;
-    a.kps = c->outkps.p;
-    a.out_n = c->outn.as<int32_t>();
-    a.out_cap = c->plan.out_cap;
-    a.xy_un = c->gxy.as<float>();
-    a.cell_start = c->gstart.as<int32_t>();
-    a.cell_idx = c->gidx.as<int32_t>();
-    a.desc = c->outdesc.as<uint8_t>();
-    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
-    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
-    a.window = (float)window_size;
-    a.nnratio = nnratio;
-    a.check_orientation = check_orientation != 0;
-    a.match12 = c->inimatch.as<int32_t>();
-    a.prev_out = c->inipout.as<float>();
-    a.nmatches = c->ininm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    r = timed(c, ST_SBP, s, [&] { return launch_init_search(a, n_pairs, s); });
-    if (r) return r;
-    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
-    c->init_pairs.assign(image_pairs, image_pairs + 2 * np);
-    c->need_fork = true;
-    return ORBGPU_OK;
-}
-
-int orbgpu_download_initialization_matches(orbgpu_ctx* c, int pair, int32_t* match12, float* prev_matched, int cap,
-                                           int* n1, int* nmatches, int32_t rot_hist[30]) {
-    if (!c || pair < 0 || (size_t)pair >= c->init_pairs.size() / 2) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    const size_t np = c->init_pairs.size() / 2, o = (size_t)pair * c->plan.out_cap;
-    int32_t nk = 0, nm = 0;
-    D2H(&nk, c->outn.as<int32_t>() + c->init_pairs[2 * (size_t)pair], 4);
-    D2H(&nm, c->ininm.as<int32_t>() + pair, 4);
-    if (int e = count_status(nk)) return e;
-    if (n1) *n1 = nk;
-    if (nmatches) *nmatches = nm;
-    if (rot_hist) D2H(rot_hist, c->ininm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
-    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    if (match12 && nk) D2H(match12, c->inimatch.as<int32_t>() + o, 4 * (size_t)nk);
-    if (prev_matched && nk) D2H(prev_matched, c->inipout.as<float>() + 2 * o, 8 * (size_t)nk);
-    return ORBGPU_OK;
-}
-
-// ---- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (orb_bow.hip) -------------------------------
-static_assert(sizeof(orbgpu_bow_point) == 44 && sizeof(BowPoint) == 44, "orbgpu_bow_point is 44 bytes");
-static_assert(ORBGPU_BOW_MAX_POINTS == kBowMaxPoints, "the header states the grouping kernel's limit");
-
-int orbgpu_search_by_bow_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const orbgpu_bow_point* kf_pts,
-                               const int32_t* kf_offsets, const int32_t* f_nodes, int node_stride, float nnratio,
-                               int check_orientation, void* stream) {
-    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
-    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
-    if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !f_nodes)) return fail(ORBGPU_ERR_INVALID, "null array");
-    for (int p = 0; p < n_pairs; ++p)
-        if (frames[p] < 0 || frames[p] >= c->last_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_run_batch");
-    if (n_pairs > 0 && kf_offsets[0] < 0) return fail(ORBGPU_ERR_INVALID, "negative keyframe offset");
-    for (int p = 0; p < n_pairs; ++p)
-        if (kf_offsets[p + 1] < kf_offsets[p]) return fail(ORBGPU_ERR_INVALID, "kf_offsets must ascend");
-    if (n_pairs > 0 && node_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative node_stride");
-    if (n_pairs == 0) {
-        c->bow_frames.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
-    {  // one row of node_stride nodes per pair: it must cover the frame's keypoints
-        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-        std::vector<int32_t> counts((size_t)c->last_images);
-        D2H(counts.data(), c->outn.p, counts.size() * 4);
-        for (int p = 0; p < n_pairs; ++p)
-            if (node_stride < std::min(counts[frames[p]], (int32_t)cap))
-                return fail(ORBGPU_ERR_INVALID, "node_stride below the frame's keypoint count");
-    }
-    int max_side = (int)cap;
-    for (int p = 0; p < n_pairs; ++p) max_side = std::max(max_side, kf_offsets[p + 1] - kf_offsets[p]);
-    if (max_side > kBowMaxPoints)
-        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
-    // pair p's keyframe points from 0 on the device
-    std::vector<int32_t> head(2 * np + 1);
-    std::copy(frames, frames + np, head.begin());
-    for (size_t p = 0; p <= np; ++p) head[np + p] = kf_offsets[p] - kf_offsets[0];
-    const size_t nkf = (size_t)head[2 * np];
-    HIP_TRY(hipSetDevice(c->device));
-    // bowgrp: kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order, f_seg_node [np * cap
-    // each], f_seg_start [np * (cap + 1)], nseg [2 np]
-    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
-    if (c->bowin.ensure(head.size() * 4 + 256) || c->bowkf.ensure(nkf * sizeof(BowPoint) + 256) ||
-        c->bowfn.ensure(np * cap * 4 + 256) || c->bowgrp.ensure(grp_words * 4 + 256) ||
-        c->bowdesc.ensure(np * cap * 32 + 256) || c->bowmatch.ensure(np * cap * 5 + 256) ||
-        c->bownm.ensure(np * (1 + kRotBins) * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (bag-of-words search)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int r = join_all(c, s);  // keypoints and descriptors come from the chunk streams
-    if (r) return r;
-    // host inputs are pageable: copy, then wait so the caller may reuse them on return
-    HIP_TRY(hipMemcpyAsync(c->bowin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-    if (nkf)
-        HIP_TRY(hipMemcpyAsync(c->bowkf.p, kf_pts + kf_offsets[0], nkf * sizeof(BowPoint), hipMemcpyHostToDevice, s));
-    if (const size_t w = std::min((size_t)node_stride, cap) * 4)
-        HIP_TRY(hipMemcpy2DAsync(c->bowfn.p, cap * 4, f_nodes, (size_t)node_stride * 4, w, np, hipMemcpyHostToDevice, s));
-    BowArgs a{};
-    a.frames = c->bowin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.kf_pts = c->bowkf.as<BowPoint>();
-    a.f_nodes = c->bowfn.as<int32_t>();
-    a.kps = c->outkps.p;
-    a.out_n = c->outn.as<int32_t>();
-    a.out_cap = c->plan.out_cap;
-    a.desc = c->outdesc.as<uint8_t>();
-    a.nnratio = nnratio;
-    a.check_orientation = check_orientation != 0;
-    a.kf_order = c->bowgrp.as<int32_t>();
-    a.kf_seg_node = a.kf_order + nkf;
-    a.kf_seg_start = a.kf_seg_node + nkf;
-    a.f_order = a.kf_seg_start + nkf + np;
-    a.f_seg_node = a.f_order + np * cap;
-    a.f_seg_start = a.f_seg_node + np * cap;
-    a.nseg = a.f_seg_start + np * (cap + 1);
-    a.f_desc = c->bowdesc.as<uint8_t>();
-    a.match = c->bowmatch.as<int32_t>();
-    a.match_bin = reinterpret_cast<uint8_t*>(a.match + np * cap);
-    a.nmatches = c->bownm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    r = timed(c, ST_SBP, s, [&] { return launch_bow_search(a, n_pairs, max_side, s); });
-    if (r) return r;
-    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
-    c->bow_frames.assign(frames, frames + np);
-    c->need_fork = true;
-    return ORBGPU_OK;
-}
-
-int orbgpu_download_bow_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
-                                int32_t rot_hist[30]) {
-    if (!c || pair < 0 || (size_t)pair >= c->bow_frames.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    const size_t np = c->bow_frames.size(), o = (size_t)pair * c->plan.out_cap;
-    int32_t nk = 0, nm = 0;
-    D2H(&nk, c->outn.as<int32_t>() + c->bow_frames[(size_t)pair], 4);
-    D2H(&nm, c->bownm.as<int32_t>() + pair, 4);
-    if (int e = count_status(nk)) return e;
-    if (n_kp) *n_kp = nk;
-    if (nmatches) *nmatches = nm;
-    if (rot_hist) D2H(rot_hist, c->bownm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
-    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    if (match && nk) D2H(match, c->bowmatch.as<int32_t>() + o, 4 * (size_t)nk);
-    return ORBGPU_OK;
-}
-
-// ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (orb_reloc.hip) ----
-static_assert(sizeof(orbgpu_reloc_point) == 60 && sizeof(RelocPoint) == 60, "orbgpu_reloc_point is 60 bytes");
-static_assert(sizeof(orbgpu_reloc_pose) == 60 && sizeof(RelocPose) == 60, "orbgpu_reloc_pose is 60 bytes");
-
-namespace {
-
-// MapPoint::PredictScale before its clamps (MapPoint.cc:541): log(float) is the host libm's logf
-int predicted_scale(float ratio, float log_scale) { return (int)std::ceil(std::log(ratio) / log_scale); }
-
-// thresholds[n] = the largest float r with ceilf(logf(r) / logf(scale_factor)) <= n, by bisection over the
-// bit patterns of the positive floats (the step function is monotone in r)
-void predict_scale_table(float scale_factor, int nlevels, float* thresholds) {
-    const float log_scale = std::log(scale_factor);
-    auto as_float = [](uint32_t b) {
-        float f;
-        std::memcpy(&f, &b, 4);
-        return f;
-    };
-    for (int n = 0; n + 1 < nlevels; ++n) {
-        uint32_t lo = 0x00000001u, hi = 0x7F7FFFFFu;  // the predicate holds at lo
-        if (predicted_scale(as_float(hi), log_scale) <= n) lo = hi;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (predicted_scale(as_float(mid), log_scale) <= n) lo = mid; else hi = mid;
-        }
-        thresholds[n] = as_float(lo);
-    }
-}
-
-}  // namespace
-
-int orbgpu_predict_scale_table(float scale_factor, int nlevels, float* thresholds) {
-    if (!(scale_factor > 1.0f) || !std::isfinite(scale_factor) || nlevels < 1 || nlevels > kMaxLevels ||
-        (nlevels > 1 && !thresholds))
-        return fail(ORBGPU_ERR_INVALID, "scale_factor above 1, nlevels in [1, 16] and a table of nlevels - 1 entries");
-    predict_scale_table(scale_factor, nlevels, thresholds);
-    return ORBGPU_OK;
-}
-
-int orbgpu_reloc_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const orbgpu_reloc_point* pts,
-                                     const int32_t* kf_offsets, const orbgpu_reloc_pose* poses, const float K[4],
-                                     const uint8_t* kp_block, int kp_stride, float th, int orb_dist,
-                                     int check_orientation, void* stream) {
-    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
-    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
-    if (orb_dist < 0 || orb_dist > 255) return fail(ORBGPU_ERR_INVALID, "orb_dist outside [0, 255]");
-    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ORBGPU_ERR_INVALID, "th negative or not finite");
-    if (n_pairs > 0 && (!frames || !kf_offsets || !poses || !K)) return fail(ORBGPU_ERR_INVALID, "null array");
-    for (int p = 0; p < n_pairs; ++p)
-        if (frames[p] < 0 || frames[p] >= c->grid_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
-    if (n_pairs > 0 && kf_offsets[0] < 0) return fail(ORBGPU_ERR_INVALID, "negative keyframe offset");
-    int max_pts = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        if (kf_offsets[p + 1] < kf_offsets[p]) return fail(ORBGPU_ERR_INVALID, "kf_offsets must ascend");
-        max_pts = std::max(max_pts, kf_offsets[p + 1] - kf_offsets[p]);
-    }
-    if (n_pairs > 0 && kf_offsets[n_pairs] > kf_offsets[0] && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
-    if (n_pairs > 0 && kp_block && kp_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative kp_stride");
-    if (n_pairs > 0 && reloc_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
-        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if (n_pairs == 0) {
-        c->reloc_frames.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
-    if (kp_block) {  // one row of kp_stride flags per pair: it must cover the frame's keypoints
-        if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-        std::vector<int32_t> counts((size_t)c->grid_images);
-        D2H(counts.data(), c->outn.p, counts.size() * 4);
-        for (int p = 0; p < n_pairs; ++p)
-            if (kp_stride < std::min(counts[frames[p]], (int32_t)cap))
-                return fail(ORBGPU_ERR_INVALID, "kp_stride below the frame's keypoint count");
-    }
-    // pair p's points from 0 on the device
-    std::vector<int32_t> head(2 * np + 1);
-    std::copy(frames, frames + np, head.begin());
-    for (size_t p = 0; p <= np; ++p) head[np + p] = kf_offsets[p] - kf_offsets[0];
-    const size_t total = (size_t)head[2 * np];
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->relin.ensure(head.size() * 4 + 256) || c->relpt.ensure(total * sizeof(RelocPoint) + 256) ||
-        c->relpose.ensure(np * sizeof(RelocPose) + 256) || c->relcand.ensure(total * sizeof(RelocCand) + 256) ||
-        c->relmatch.ensure(np * cap * 4 + 256) || c->relnm.ensure(np * (1 + kRotBins) * 4 + 256) ||
-        (kp_block && c->relblk.ensure(np * cap + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (relocalisation search)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int r = join_all(c, s);  // keypoints and grid come from the chunk streams
-    if (r) return r;
-    // host inputs are pageable: copy, then wait so the caller may reuse them on return
-    HIP_TRY(hipMemcpyAsync(c->relin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-    if (total)
-        HIP_TRY(hipMemcpyAsync(c->relpt.p, pts + kf_offsets[0], total * sizeof(RelocPoint), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->relpose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
-    if (kp_block) {
-        HIP_TRY(hipMemsetAsync(c->relblk.p, 0, np * cap, s));
-        if (const size_t w = std::min((size_t)kp_stride, cap))
-            HIP_TRY(hipMemcpy2DAsync(c->relblk.p, cap, kp_block, kp_stride, w, np, hipMemcpyHostToDevice, s));
-    }
-    RelocArgs a{};
-    a.frames = c->relin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.pts = c->relpt.as<RelocPoint>();
-    a.poses = c->relpose.as<RelocPose>();
-    a.cand = c->relcand.as<RelocCand>();
-    a.kps = c->outkps.p;
-    a.out_n = c->outn.as<int32_t>();
-    a.out_cap = c->plan.out_cap;
-    a.xy_un = c->gxy.as<float>();
-    a.cell_start = c->gstart.as<int32_t>();
-    a.cell_idx = c->gidx.as<int32_t>();
-    a.desc = c->outdesc.as<uint8_t>();
-    a.kp_block = kp_block ? c->relblk.as<uint8_t>() : nullptr;
-    std::memcpy(a.bounds, c->grid_bounds, sizeof a.bounds);
-    std::memcpy(a.grid_inv, c->grid_inv, sizeof a.grid_inv);
-    for (int l = 0; l < kMaxLevels; ++l) a.scale[l] = l < c->prm.nlevels ? c->tab.scale[l] : 1.0f;
-    a.nlevels = c->prm.nlevels;
-    predict_scale_table(c->prm.scale_factor, c->prm.nlevels, a.level_step);  // Frame.cc:132 + MapPoint.cc:541
-    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
-    a.th = th;
-    a.orb_dist = orb_dist;
-    a.check_orientation = check_orientation != 0;
-    a.match = c->relmatch.as<int32_t>();
-    a.nmatches = c->relnm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    r = timed(c, ST_SBP, s, [&] { return launch_reloc(a, n_pairs, max_pts, s); });
-    if (r) return r;
-    HIP_TRY(hipStreamSynchronize(s));  // the pageable uploads above
-    c->reloc_frames.assign(frames, frames + np);
-    c->need_fork = true;
-    return ORBGPU_OK;
-}
-
-int orbgpu_download_reloc_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
-                                  int32_t rot_hist[30]) {
-    if (!c || pair < 0 || (size_t)pair >= c->reloc_frames.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
-    const size_t np = c->reloc_frames.size(), o = (size_t)pair * c->plan.out_cap;
-    int32_t nk = 0, nm = 0;
-    D2H(&nk, c->outn.as<int32_t>() + c->reloc_frames[(size_t)pair], 4);
-    D2H(&nm, c->relnm.as<int32_t>() + pair, 4);
-    if (int e = count_status(nk)) return e;
-    if (n_kp) *n_kp = nk;
-    if (nmatches) *nmatches = nm;
-    if (rot_hist) D2H(rot_hist, c->relnm.as<int32_t>() + np + (size_t)pair * kRotBins, 4 * kRotBins);
-    if (nk > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    if (match && nk) D2H(match, c->relmatch.as<int32_t>() + o, 4 * (size_t)nk);
     return ORBGPU_OK;
 }
 

@@ -15,7 +15,7 @@
 //
 // The predicted level is ceil(log(ratio) / log(scaleFactor)) with the host libm's logf; the device
 // library's need not equal it near a step.  The level is a step function of the ratio, so the host
-// finds the steps once (predict_scale_table, orb_post.cpp) and the device counts the steps below
+// finds the steps once (predict_scale_table, orb_matchers.cpp) and the device counts the steps below
 // the ratio: no logarithm runs here.
 //
 // The loop is sequential -- a keypoint taken by a point is skipped by every later point -- so, as
@@ -43,7 +43,6 @@ namespace orbgpu {
 namespace {
 
 constexpr int kTop = 4;
-constexpr int kNoBin = 31;  // an event outside [0, 30), or no orientation check
 
 __device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
@@ -71,11 +70,8 @@ __global__ __launch_bounds__(256) void k_reloc_candidates(RelocArgs a) {
     if (!(pt.flags & kRpValid)) return;  // :1941-1944
     const RelocPose T = a.poses[p];
     const float X = pt.pos[0], Y = pt.pos[1], Z = pt.pos[2];
-    const float xc = ((T.Rcw[0] * X + T.Rcw[1] * Y) + T.Rcw[2] * Z) + T.tcw[0];
-    const float yc = ((T.Rcw[3] * X + T.Rcw[4] * Y) + T.Rcw[5] * Z) + T.tcw[1];
-    const float zc = ((T.Rcw[6] * X + T.Rcw[7] * Y) + T.Rcw[8] * Z) + T.tcw[2];
-    const float u = a.K[0] * xc / zc + a.K[2];
-    const float v = a.K[1] * yc / zc + a.K[3];
+    float xc, yc, zc, u, v;
+    project_pinhole(T.Rcw, T.tcw, a.K, pt.pos, &xc, &yc, &zc, &u, &v);
     if (u < a.bounds[0] || u > a.bounds[1]) return;  // :1953-1956
     if (v < a.bounds[2] || v > a.bounds[3]) return;
     if (!isfinite(u) || !isfinite(v)) return;
@@ -99,16 +95,7 @@ __global__ __launch_bounds__(256) void k_reloc_candidates(RelocArgs a) {
                 [&](int k, int d, int) {
                     if (d > a.orb_dist) return;  // can never become an event (:2004)
                     ++c.n;
-                    bool shift = false;  // (distance, window position) order: after equal distances
-#pragma unroll
-                    for (int t = 0; t < kTop; ++t) {
-                        shift = shift || d < c.dist[t];
-                        if (shift) {
-                            const int ti = c.idx[t], td = c.dist[t];
-                            c.idx[t] = k, c.dist[t] = d;
-                            k = ti, d = td;
-                        }
-                    }
+                    top4_insert(c.idx, c.dist, k, d);
                 });
     c.level = level, c.u = u, c.v = v;
     out = c;

@@ -100,16 +100,7 @@ __global__ __launch_bounds__(256) void k_track_candidates(TrackArgs a) {
     walk_window(a, F, u, v, minLevel, maxLevel, radius, u - a.mbf * invz, q, [&](int k) { return blk && blk[k]; },
                 [&](int k, int d, int) {
                     ++c.n;
-                    bool shift = false;  // (distance, window position) order: after equal distances
-#pragma unroll
-                    for (int j = 0; j < kTop; ++j) {
-                        shift = shift || d < c.dist[j];
-                        if (shift) {
-                            const int ti = c.idx[j], td = c.dist[j];
-                            c.idx[j] = k, c.dist[j] = d;
-                            k = ti, d = td;
-                        }
-                    }
+                    top4_insert(c.idx, c.dist, k, d);
                 });
     c.u = u, c.v = v, c.invz = invz;
     out = c;
@@ -236,12 +227,8 @@ __device__ inline int track_replay(const Args& a, const FrameView& F, const Repl
                 if (obs) atomicOr(&taken[ak >> 5], 1u << (ak & 31));
             }
             if (ev && a.check_orientation) {  // :1829-1837
-                float rot = c.angle - angle_of(F, ak);
-                if (rot < 0.0f) rot += 360.0f;
-                const float b = roundf(rot * (1.0f / 30));
-                if (b >= 0.f && b <= 30.f) {
-                    int bin = (int)b;
-                    if (bin == kRotBins) bin = 0;
+                uint32_t bin;
+                if (rot_bin(c.angle, angle_of(F, ak), &bin)) {
                     atomicAdd(&hist[bin], 1u);
                     atomicOr(&binmask[ak], 1u << bin);
                 }
@@ -349,16 +336,7 @@ __global__ __launch_bounds__(256) void k_track_candidates_stereo(TrackStereoArgs
                     },
                     [&](int k, int d, int) {
                         ++c.n;
-                        bool shift = false;  // (distance, window position) order: after equal distances
-#pragma unroll
-                        for (int s = 0; s < kTop; ++s) {
-                            shift = shift || d < c.dist[s];
-                            if (shift) {
-                                const int ti = c.idx[s], td = c.dist[s];
-                                c.idx[s] = k, c.dist[s] = d;
-                                k = ti, d = td;
-                            }
-                        }
+                        top4_insert(c.idx, c.dist, k, d);
                     });
         c.u = u, c.v = v;
     }

@@ -1,7 +1,8 @@
 // orb_window.h -- Frame::GetFeaturesInArea (Frame.cc:673-739) over a frame whose keypoints,
 // descriptors, grid and mvuRight live in HBM, shared by the two projection searches
 // (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search) and, with
-// ComputeThreeMaxima, by the initialisation search (orb_init.hip).
+// ComputeThreeMaxima, by the initialisation search (orb_init.hip); the relocalisation and
+// bag-of-words searches (orb_reloc.hip, orb_bow.hip) share its candidate and rotation-bin helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,6 +140,46 @@ __device__ inline FrameView frame_view_of(const Args& a, int img, const float* u
     F.desc = a.desc + 32LL * img * a.out_cap;
     F.uright = uright;
     return F;
+}
+
+// Rcw * pos + tcw and its pinhole projection (K = {fx, fy, cx, cy}).  The build keeps the operation
+// order (no contraction): it is the result.
+__device__ inline void project_pinhole(const float Rcw[9], const float tcw[3], const float K[4], const float pos[3],
+                                       float* xc, float* yc, float* zc, float* u, float* v) {
+    const float X = pos[0], Y = pos[1], Z = pos[2];
+    *xc = ((Rcw[0] * X + Rcw[1] * Y) + Rcw[2] * Z) + tcw[0];
+    *yc = ((Rcw[3] * X + Rcw[4] * Y) + Rcw[5] * Z) + tcw[1];
+    *zc = ((Rcw[6] * X + Rcw[7] * Y) + Rcw[8] * Z) + tcw[2];
+    *u = K[0] * *xc / *zc + K[2];
+    *v = K[1] * *yc / *zc + K[3];
+}
+
+// Candidate k at distance d into the four lowest (distance, window position) records: the candidates
+// come in window order, so k goes after the records of equal distance.
+__device__ inline void top4_insert(int32_t idx[4], int32_t dist[4], int k, int d) {
+    bool shift = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        shift = shift || d < dist[j];
+        if (shift) {
+            const int ti = idx[j], td = dist[j];
+            idx[j] = k, dist[j] = d;
+            k = ti, d = td;
+        }
+    }
+}
+
+// The histogram bin of rot = angle_a - angle_b as ORBmatcher.cc:1829-1837 finds it (no fmodf: the angles
+// lie in [0, 360)); false, and *bin as it was, where the reference's assert would fail.
+constexpr int kNoBin = 31;  // what the callers keep for such an event, or without an orientation check
+__device__ inline bool rot_bin(float angle_a, float angle_b, uint32_t* bin) {
+    float rot = angle_a - angle_b;
+    if (rot < 0.0f) rot += 360.0f;
+    const float rb = roundf(rot * (1.0f / 30));
+    if (!(rb >= 0.f && rb <= 30.f)) return false;
+    *bin = (uint32_t)(int)rb;
+    if (*bin == kRotBins) *bin = 0;
+    return true;
 }
 
 // ComputeThreeMaxima (ORBmatcher.cc:2061-2102) on hist[0 .. kRotBins) by one lane: hist[kRotBins] = the set of
