@@ -12,7 +12,9 @@
 // order are row-major and ordered output needs only a prefix over waves.  Per threshold t:
 // (1) the antipodal-pair pre-test (fw_pretest4) on 4 pixels per lane, passing pixels compacted
 // into the wave list; (2) the exact strength m (orb_math.h fast_strength_packed) of every
-// candidate, m > t being the segment test itself; (3) the 3x3 nonmax over the corners.
+// candidate, m > t being the segment test itself; (3) the 3x3 nonmax over the corners.  With
+// several waves per cell (3) marks the kept corners and an ordered pass writes their keys after
+// the waves have exchanged counts; one wave per cell writes each key in (3) itself.
 // Policy-templated like orb_octree.h so the host harness runs the same code on the CPU.
 #pragma once
 #ifndef FAST_THREADS
@@ -22,6 +24,8 @@
 #endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "orb_math.h"
 #include "orb_octree.h"
@@ -64,6 +68,32 @@ __host__ __device__ inline bool fast_kept(const uint8_t* M, int off, int t) {
     const int a = imax(imax(q0, q1), imax(q2, q3)), b = imax(imax(q4, q5), imax(q6, q7));
     return (v > t) & (v >= 2) & (imax(a, b) < v);
 }
+
+// The same verdict as one compare, device only: m > t, m >= 2 and m > max(q) <=> m > max(q, t, 1).
+// t1 = max(t, 1) (wave-uniform, < 256) joins the neighbours' max tree: nine inputs are four
+// 3-input maxima, as eight are, so the two threshold compares and their ANDs cost nothing.
+// The nine loads share one address, that of the upper left neighbour (an LDS load's immediate
+// offset is unsigned: from &M[off] the four offsets below it cost one VALU each).  Returns m
+// through *mv.
+template <int P>
+__device__ inline bool fast_kept1(const uint8_t* M, int off, int t1, int* mv) {
+    int ul = off - P - 1;
+    asm volatile("" : "+v"(ul));  // keep the address (not re-based on off)
+    const uint8_t* m = &M[ul];
+    const int v = m[P + 1];
+    const int q0 = m[0], q1 = m[1], q2 = m[2], q3 = m[P];
+    const int q4 = m[P + 2], q5 = m[2 * P], q6 = m[2 * P + 1], q7 = m[2 * P + 2];
+    const int a = imax(imax(q0, q1), q2), b = imax(imax(q3, q4), q5), c = imax(imax(q6, q7), t1);
+    *mv = v;
+    return imax(imax(a, b), c) < v;
+}
+
+// One wave per cell, a compile-time property of the policy (Pol::kOneWavePerCell; policies
+// without the member, the host harness's among them, do not have it): see fast_cell_detect.
+template <class Pol, class = void>
+struct fast_one_wave_cell : std::false_type {};
+template <class Pol>
+struct fast_one_wave_cell<Pol, std::void_t<decltype(Pol::kOneWavePerCell)>> : std::bool_constant<Pol::kOneWavePerCell> {};
 
 typedef unsigned short fw_u16x2 __attribute__((ext_vector_type(2)));
 
@@ -432,6 +462,51 @@ __host__ __device__ int fast_cell_detect(Pol& p, int sh, const CellGeom& g, int 
         }
         return nb;
     };
+    if constexpr (fast_one_wave_cell<Pol>::value) {
+        // One wave per cell: no other wave's kept count comes before this wave's keys, so the
+        // nonmax pass writes each kept corner's key at once, at the running kept count.  The
+        // list is not written (no verdict bit) and not read a second time.  A pass that keeps
+        // nothing writes nothing, so the minThFAST rerun starts from untouched output.
+        // The key's fields do not overlap (x, y < 4096, cornerScore<16> = m - 1 in [1, 254]), so
+        // make_key(x, y, m - 1) is the sum kb + o + r (4096 - CP) + (m << 24) with
+        // o = r CP + (c + sh): the or-chain as one 24-bit multiply-add and one shift-add.
+        const uint32_t kb = (uint32_t)(g.iniX - sh - g.minBorder) + ((uint32_t)(g.iniY - g.minBorder) << 12) - (1u << 24);
+        auto emit_kept = [&](int nb, int t) {
+            // max(t, 1) once, as a scalar of 8 known bits (readfirstlane: the compiler otherwise
+            // moves the max with 1 into the loop's vector code)
+            const int t1 = __builtin_amdgcn_readfirstlane(imax(t, 1)) & 0xFF;
+            int run = 0;
+            for (int base = 0; base < nb; base += L) {
+                const int j = base + lane;
+                const int o = list[imin(j, nb - 1)];  // tail lanes re-test the last entry
+                int mv;
+                const bool in = j < nb, top = fast_kept1<CP>(M, o, t1, &mv);
+                const bool k = in & top;
+                const uint64_t m = p.ballot(in) & p.ballot(top);  // two compares' masks, ANDed on the SALU
+                if (k) {
+                    const uint32_t r = (uint32_t)o / (uint32_t)CP;
+                    uint32_t* const out = keys_out + run;  // wave-uniform base, 32-bit lane offset
+                    out[(uint32_t)p.rank(m)] = kb + ((uint32_t)o + r * (uint32_t)(4096 - CP)) + ((uint32_t)mv << 24);
+                }
+                run += p.popc64(m);
+            }
+            return run;
+        };
+        int nb = build(tini);
+        if (kCapped && nb == kFastOverflow) return kFastOverflow;
+        p.sync();  // M complete
+        int n = emit_kept(nb, tini);
+        if (n == 0) {  // the cell kept nothing at iniThFAST: rerun at minThFAST (:845-861)
+            p.sync();
+            if (tmin < tini) {
+                nb = build(tmin);
+                if (kCapped && nb == kFastOverflow) return kFastOverflow;
+                p.sync();
+            }
+            n = emit_kept(nb, tmin);
+        }
+        return n;
+    }
     // nonmax at t for every corner of the list; the verdict is kept in bit 15 of the entry
     // (LDS offsets < 6400 use 13 bits) for the ordered write
     auto count_kept = [&](int nb, int t) {

@@ -793,6 +793,13 @@ hipError_t launch_pyr_tail(const BatchArgs& a, hipStream_t s) {
 // detection on [3,rows-3)x[3,cols-3) of the cell ROI, 3x3 nonmax inside the cell only, iniTh
 // then minTh if the cell yields nothing, keys emitted in row-major order.
 
+// k_fast_cells' policy.  A 64-thread workgroup is one wave per cell: the wave's corner list is
+// the cell's, so fast_cell_detect writes the keys in its nonmax pass (orb_fast_cell.h).
+template <int NT>
+struct FastCellPolicy : FixedDevPolicy<NT> {
+    static constexpr bool kOneWavePerCell = NT == 64;
+};
+
 // One cell of image img (flattened cell index gcell) with a candidate list of kCap entries;
 // returns the kept count (written to the cell's count) or kFastOverflow (nothing written).
 template <int CP, int kCap>
@@ -830,7 +837,7 @@ __device__ __attribute__((always_inline)) inline int fast_cell_one(const BatchAr
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, roi32 + (int)off, 0, 0);
         return make_uint4(v[0], v[1], v[2], v[3]);
     };
-    FixedDevPolicy<kFastThreads> p{{scratch}};
+    FastCellPolicy<kFastThreads> p{{{scratch}}};
     fast_cell_tables<CP>(g, sh, lut, emask);  // synced with the ROI staging (fast_cell_run)
     CellScratch cs{T, M, list, wcnt, lut, emask, wovf};
     const int n = fast_cell_run<CP, kCap>(p, src, G.pitch, sh, dword_ok, g, a.ini_th, a.min_th, cs, key_out, ld16);
