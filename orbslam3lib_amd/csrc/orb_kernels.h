@@ -114,6 +114,7 @@ struct BatchArgs {
     int fuse_out;              // no image of the batch has a lapping area: k_orient_desc writes the
                                // assembled outputs and counts, k_finalize does not run
 };
+static_assert(sizeof(BatchArgs) <= 4096, "kernel argument block too large");
 
 struct MatchArgs {
     const uint8_t* desc;      // out_desc
@@ -139,7 +140,7 @@ struct MatchArgs {
 #endif
 constexpr int kKnnMaxSplit = KNN_SPLIT;     // train-row splits of a launch with few pairs
 constexpr int kKnnSplitSlots = KNN_SPLIT;   // pairs x splits the partial buffer holds (1 pair: KNN_SPLIT splits)
-// queries per k_knn2_mfma_pairs workgroup (orb_kernels.hip); the grid's x extent is
+// queries per k_knn2_mfma_pairs workgroup (orb_knn2.hip); the grid's x extent is
 // ceil(out_cap / kKnnQueries) query blocks per pair
 constexpr int kKnnQueries = 256;
 // arrival counters of the fused split merge: one per (pair of the launch, query block); a split
@@ -220,10 +221,45 @@ constexpr int kOdBlockKps = 3 * kOdKpBlock;
 
 constexpr int kOctLdsKeys = 16384;  // per-key node labels (u16) kept in LDS up to this many keys
 constexpr int kFastMergeMaxImages = 4;  // launches this small run the 48/64 FAST cells as one launch
-// candidate list of the small-list k_fast_cells<48> / <64> (orb_kernels.hip), split over the waves
+// candidate list of the small-list k_fast_cells<48> / <64> (orb_fast.hip), split over the waves
 template <int CP>
 constexpr int kFastSmallList() { return CP == 48 ? 512 : 1280; }
 constexpr int kFastOvfBlocks = 32;      // workgroups of k_fast_cells_ovf
+// FAST cells of the levels that run the `tile`-byte LDS tile (48, 64 or kCellMax = 80): their
+// flattened cell range (smaller tiles = less LDS per workgroup = more cells resident per CU)
+inline void fast_cell_range(const BatchArgs& a, int tile, int* c0, int* c1) {
+    *c0 = tile == 48 ? 0 : tile == 64 ? a.fast_n48 : a.fast_n64;
+    *c1 = tile == 48 ? a.fast_n48 : tile == 64 ? a.fast_n64 : a.total_cells;
+}
+// What launch_fast_cells(a, tile) launches.  Pure host code: it reads nimages, fast_small,
+// fast_n48, fast_n64, total_cells and whether fast_ovf is bound.
+struct FastLaunchPlan {
+    int tile;    // k_fast_cells<tile, small> over the cells [c0, c1); 0: the call launches nothing
+    int c0, c1;
+    bool small;  // the small-list kernel
+    bool ovf;    // k_fast_cells_ovf<64> follows it
+};
+inline FastLaunchPlan fast_launch_plan(const BatchArgs& a, int tile) {
+    int c0, c1;
+    fast_cell_range(a, tile, &c0, &c1);
+    // a launch of a few images (the latency shape) leaves the GPU mostly idle: the 48- and 64-byte
+    // cells go in ONE 64-byte launch instead of two back to back (every 48 cell fits 64)
+    const bool merge = a.nimages <= kFastMergeMaxImages && a.fast_small <= 0 && a.fast_n48 > 0 && a.fast_n64 > a.fast_n48;
+    if (merge && tile == 64) return {};  // done by the 48 call
+    if (merge && tile == 48) {
+        tile = 64;
+        c1 = a.fast_n64;
+    }
+    if (c1 <= c0) return {};
+    // the small-list 48- and 64-byte kernels for the batch shape (a.fast_small); the two tiles'
+    // launches share the queue slot (one after the other on the stream)
+    const bool small = (tile == 48 || tile == 64) && a.fast_ovf &&
+                       (a.fast_small > 0 || (a.fast_small < 0 && a.nimages > kFastMergeMaxImages));
+    // one overflow pass after both tiles, so after the 48-byte launch only when no 64-byte one
+    // follows: the 64-byte full-list kernel redoes the cells either queued and resets the queue
+    const bool ovf = small && (tile == 64 || a.fast_n64 <= a.fast_n48);
+    return {tile, c0, c1, small, ovf};
+}
 constexpr int kOctSmallThreads = 256;  // default workgroup size of the short-level k_octree launch
 constexpr int kOctSmallMinImages = 32;  // launches with fewer images keep the 512-thread shape
 // default dynamic LDS of that launch: a 640x480 level 0's node state (~38 KB) plus its depth-5
@@ -265,7 +301,8 @@ __host__ __device__ inline OctLayout oct_layout(int n_cap, int C) {
     return L;
 }
 
-// Kernel launchers (orb_kernels.hip).  Each returns hipGetLastError() of its launch.
+// Kernel launchers (orb_pyramid.hip, orb_fast.hip, orb_octree.hip, orb_orient.hip, orb_knn2.hip).
+// Each returns hipGetLastError() of its launch.
 // k_blur / k_blur_resize tile: kBlurTW x kBlurTH outputs of the blur (kBlurTH a multiple of 16:
 // 8 row groups of kBlurTH / 8 rows, an even count, in the vertical pass)
 #ifndef BLUR_TH
@@ -284,9 +321,7 @@ constexpr int kTailPad = 16;          // k_pyr_tail: left pad of an LDS row (>= 
 constexpr int kTailLdsMax = 160 * 1024;  // the LDS one workgroup may hold on gfx950
 constexpr int kTailMinImages = 128;     // k_pyr_tail only for launches of >= this many images
 hipError_t launch_pyr_tail(const BatchArgs& a, hipStream_t s);
-// FAST cells of the levels that run the `tile`-byte LDS tile (48, 64 or kCellMax = 80):
-// fast_cell_range gives their flattened cell range, launch_fast_cells launches nothing if empty
-void fast_cell_range(const BatchArgs& a, int tile, int* c0, int* c1);
+// one call per tile (48, 64, kCellMax = 80), each launching what fast_launch_plan says
 hipError_t launch_fast_cells(const BatchArgs& a, int tile, hipStream_t s);
 hipError_t launch_octree(const BatchArgs& a, hipStream_t s);
 hipError_t launch_orient_desc(const BatchArgs& a, hipStream_t s);

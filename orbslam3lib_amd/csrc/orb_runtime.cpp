@@ -2,8 +2,8 @@
 //
 // Owns one HIP stream and every device buffer of a context (allocated once per geometry,
 // never inside a launch sequence), sized and laid out by the pure planner of orb_geometry.h, and
-// enqueues the kernels of orb_kernels.hip.  There is no CPU compute path: every result comes from
-// the device.  What runs after a batch (matching, downloads, getters) is in orb_post.cpp; the
+// enqueues the kernels of orb_pyramid.hip, orb_fast.hip, orb_octree.hip and orb_orient.hip.  There
+// is no CPU compute path: every result comes from the device.  What runs after a batch (matching, downloads, getters) is in orb_post.cpp; the
 // context itself and the helpers both files share are in orb_ctx.h.
 #include <link.h>
 

@@ -357,4 +357,21 @@ int harness_level_candidates(const uint8_t* lvl, int w, int h, int ini, int mn, 
     return total;
 }
 
+// launch_fast_cells' decision for one tile call (orb_kernels.h fast_launch_plan), from the fields it
+// reads: out = {tile (0: nothing launched), c0, c1, small-list kernel, overflow pass follows, 0}.
+void harness_fast_launch_plan(int nimages, int fast_small, int n48, int n64, int total_cells, int has_ovf, int tile,
+                              int32_t out[6]) {
+    static int2 queue;  // only its address is looked at
+    BatchArgs a{};
+    a.nimages = nimages;
+    a.fast_small = fast_small;
+    a.fast_n48 = n48;
+    a.fast_n64 = n64;
+    a.total_cells = total_cells;
+    a.fast_ovf = has_ovf ? &queue : nullptr;
+    const FastLaunchPlan p = fast_launch_plan(a, tile);
+    const int32_t v[6] = {p.tile, p.c0, p.c1, p.small, p.ovf, 0};
+    std::memcpy(out, v, sizeof(v));
+}
+
 }  // extern "C"

@@ -1,7 +1,7 @@
 """GPU parity on the configurations the headline numbers run, and on the matcher's segment edges.
 
 * kNN2 past one 4096-row train segment (k_knn2_mfma walks train rows in 4096-row segments with a
-  12-bit local index, orb_kernels.hip knn2_mfma_block): nt in {4095, 4096, 4097, 5000, 8193} with
+  12-bit local index, orb_knn2.hip knn2_fp4_block): nt in {4095, 4096, 4097, 5000, 8193} with
   exact-duplicate rows on both sides of every segment boundary, so the cross-segment tie rule
   (lowest index wins, cv::BFMatcher k=2 / SURVEY §8 a10) is exercised.
 * The batch matcher (orbgpu_match_stereo_batch) with more than 4096 train rows per pair, and the
@@ -121,7 +121,7 @@ def test_batch_1080p_8200_repeatable(oracle, monkeypatch, pyr):
 
 def test_split_knn2_one_pair_past_4096_rows(oracle, monkeypatch):
     """A one-pair batch (the C4 shape) matches with the train rows split over 8 workgroups per
-    query block, the last of which merges the partial lists (orb_kernels.hip k_knn2_mfma_pairs'
+    query block, the last of which merges the partial lists (orb_knn2.hip k_knn2_mfma_pairs'
     counter hand-off); at 1920x1080 with 8200 features the splits straddle the 4096-row key
     segments.  Equal to the oracle on three launches in a row (the arrival counters reset
     themselves), and to the unsplit launch (ORBGPU_KNN_NOSPLIT)."""

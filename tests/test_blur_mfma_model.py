@@ -1,4 +1,4 @@
-"""CPU model of the matrix-core blur (orb_kernels.hip blur_tile_compute_mfma).
+"""CPU model of the matrix-core blur (orb_pyramid.hip blur_tile_compute_mfma).
 
 The kernel computes the 7x7 GaussianBlur of a 128 x 32 tile (ORBextractor_old.cc:1146-1147,
 OpenCV 8U fixed point: 7-tap kernel {18, 34, 48, 56, 48, 34, 18} / 256 per axis, one rounding

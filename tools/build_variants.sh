@@ -1,10 +1,15 @@
 #!/bin/bash
-# Measurement variants of liborbgpu.so: one translation unit (SRC, default orb_kernels.hip)
-# rebuilt with extra defines, linked with the other objects of the normal build.
-# Usage: [SRC=orb_fast.hip] tools/build_variants.sh NAME "-DFOO=1" [...]
+# Measurement variants of liborbgpu.so: one translation unit (SRC) rebuilt with extra defines,
+# linked with the other objects of the normal build.
+# Usage: SRC=orb_fast.hip tools/build_variants.sh NAME "-DFOO=1" [...]
 cd "$(dirname "$0")/.."
 set -e
-SRC=${SRC:-orb_kernels.hip}
+if [ -z "$SRC" ] || [ ! -f "orbslam3lib_amd/csrc/$SRC" ] || [ $# -lt 2 ]; then
+  echo "usage: SRC=<unit> $0 NAME \"-DFOO=1\" [NAME DEFS ...]" >&2
+  echo "  the extractor's units: orb_pyramid.hip orb_fast.hip orb_octree.hip orb_orient.hip orb_knn2.hip" >&2
+  echo "  (or any other file of orbslam3lib_amd/csrc that the Makefile's LIBSRC lists)" >&2
+  exit 2
+fi
 make -s orbslam3lib_amd/liborbgpu.so
 O=orbslam3lib_amd/variants
 mkdir -p $O

@@ -1,4 +1,4 @@
-"""Repeatability probe of the small-list FAST path and its overflow queue (orb_kernels.hip
+"""Repeatability probe of the small-list FAST path and its overflow queue (orb_fast.hip
 k_fast_cells<CP, true> / k_fast_cells_ovf) on a batch shaped like the bench's chunks: 24
 synthetic 640x480 stereo pairs and 8 pairs of uniform noise (whose cells overflow the capped
 lists), 64 images on the default chunk streams.  Each setting runs R batches on one context:
