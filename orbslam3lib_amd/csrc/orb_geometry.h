@@ -257,6 +257,30 @@ inline int resize_level(int l, GeomPlan& P, std::string* err) {
         if (tq[j + 1] - tq[j] > kBrMaxQuads) return invalid(err, "resize quad table");
     G.band_row_off = push_ints(band);
     G.tile_quad_off = push_ints(tq);
+    G.qrec_off = G.qbase_off = G.yrec_off = 0;
+    if (G.area2) return 0;
+    // the same tables in the form the resize loops read (orb_pyramid.hip rs_hsum / rs_vert): per
+    // output quad the taps of its four outputs relative to the quad's first left tap as v_perm
+    // selector pairs (0 .. 7 for scale steps <= 2) and the coefficient pairs times 16 as u16 pairs,
+    // per output row the weights as b << 8; the last quad repeats the last column
+    std::vector<int> qbase(nquads);
+    G.qrec_off = (int)P.rtab.size();
+    for (int q = 0; q < nquads; ++q) {
+        const int base = xt[std::min(4 * q, G.w - 1)].x;
+        unsigned sl[4], cl[4];
+        for (int k = 0; k < 4; ++k) {
+            const int4 x = xt[std::min(4 * q + k, G.w - 1)];
+            sl[k] = (unsigned)(x.x - base) | 0x0c00u | ((unsigned)(x.y - base) << 16) | 0x0c000000u;
+            cl[k] = ((unsigned)x.z << 4) | ((unsigned)x.w << 20);
+        }
+        P.rtab.push_back(make_int4((int)sl[0], (int)sl[1], (int)sl[2], (int)sl[3]));
+        P.rtab.push_back(make_int4((int)cl[0], (int)cl[1], (int)cl[2], (int)cl[3]));
+        qbase[q] = base;
+    }
+    G.yrec_off = (int)P.rtab.size();
+    for (int dy = 0; dy < G.h; ++dy)
+        P.rtab.push_back(make_int4(yt[dy].x, yt[dy].y, (int)((unsigned)yt[dy].z << 8), (int)((unsigned)yt[dy].w << 8)));
+    G.qbase_off = push_ints(qbase);
     return 0;
 }
 

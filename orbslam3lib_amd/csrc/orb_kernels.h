@@ -48,6 +48,11 @@ struct LevelGeom {
     // first source row is >= 32 b (tiles_y(l-1) + 1 entries), tile_quad[j] = first quad whose first
     // source column is >= 128 j (tiles_x(l-1) + 1 entries)
     int band_row_off, tile_quad_off;
+    // the resize tables as the resize reads them (levels >= 1 that are not area2), written once by
+    // the host: qrec_off = rtab index of two int4 per output quad (its four tap selector pairs, its
+    // four coefficient pairs times 16), qbase_off = int view of rtab: the quad's first left tap,
+    // yrec_off = rtab index of one int4 per output row {sy0, sy1, b0 << 8, b1 << 8}
+    int qrec_off, qbase_off, yrec_off;
     int od_blocks, od_first;   // orientation/descriptor blocks for this level
     int tpitch;                // k_pyr_tail: LDS row pitch of this level (levels >= tail0 - 1)
 };
@@ -314,6 +319,28 @@ constexpr int kBrMaxQuads = 40;  // k_blur_resize: level-l column quads / rows o
 constexpr int kBrMaxRows = kBlurTH + 2;
 // The blur of level l - 1 and the resize to level l in one launch (every level except the last
 // blur, which launch_blur_level does).
+// The resize loop's work split (k_blur_resize per tile, k_pyr_tail per level): thread t of nthreads
+// makes output quad q of the nq owned ones for the run of consecutive owned rows [row0, row1), so
+// that a row's second source row can serve as the next row's first (resize_row_carried).  The
+// threads form nthreads / nq slots per quad and the nrows rows are cut into that many runs of
+// ceil(nrows / slots) rows; a run is empty (row0 >= row1) beyond the last row, which covers the
+// threads beyond the last slot too (slots * len >= nrows).
+// div(n, d) = n / d for 0 <= n <= nthreads + nrows, d >= 1 (the kernels pass a reciprocal form).
+struct ResizeRun {
+    int q, row0, row1;
+};
+template <class Div>
+__host__ __device__ inline ResizeRun resize_run(int t, int nq, int nrows, int nthreads, Div div) {
+    const int d = div(nthreads, nq);
+    const int slots = d > 1 ? d : 1;
+    const int j = div(t, nq);
+    const int len = div(nrows + slots - 1, slots);
+    const int row0 = j * len;
+    return {t - j * nq, row0, row0 + len < nrows ? row0 + len : nrows};
+}
+// Inside a run: the horizontal sums of row dy's first source row sy0 are the ones the row before
+// formed for its second source row prev_sy1 (-1 at a run's first row: nothing carried yet).
+__host__ __device__ inline bool resize_row_carried(int prev_sy1, int sy0) { return prev_sy1 == sy0; }
 hipError_t launch_blur_resize(const BatchArgs& a, int level, hipStream_t s);
 hipError_t launch_blur_level(const BatchArgs& a, int level, hipStream_t s);
 hipError_t launch_level_linear(const BatchArgs& a, int level, hipStream_t s);  // scale steps > 2

@@ -33,31 +33,40 @@ __device__ inline uint32_t as_u32(u16x2 x) { return __builtin_bit_cast(uint32_t,
 // each ((D >> 4) b) >> 16 is one v_mul_hi_u32_u24 of two 24-bit operands (the 48-bit product
 // >> 32); the sum is <= 1022 (c0 + c1 = b0 + b1 = 2048), so no clamp is needed.  FixedPtCast
 // after simd_end (only the last quads of a row take that branch).
+// The two halves are separate functions because consecutive output rows share source rows: at scale
+// 1.2 row dy + 1's first source row is row dy's second one in 4 of 5 steps, so a thread that walks
+// a run of consecutive rows (resize_run) keeps that row's four sums instead of forming them again.
 // (a * b) >> 32 for 24-bit a, b: one v_mul_hi_u32_u24 (the masks tell the compiler the operand
-// widths; both are no-ops on rs_quad's operands)
+// widths; both are no-ops on rs_vert's operands)
 __device__ inline uint32_t mulhi_u24(uint32_t a, uint32_t b) {
     return (uint32_t)(((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu)) >> 32);
 }
 
-__device__ inline uint32_t rs_quad(const uint8_t* r0, const uint8_t* r1, int base, int4 sel, int4 cw, int B0,
-                                   int B1, int dx0, int simd_end) {
-    const uint32_t* p0 = reinterpret_cast<const uint32_t*>(r0 + (base & ~3));
-    const uint32_t* p1 = reinterpret_cast<const uint32_t*>(r1 + (base & ~3));
+// resize_run's divisions: n / d by v_rcp_f32 (1 ulp).  (n + 0.5) / d lies >= 0.5 / d from an integer
+// and the product's error is below 3e-7 n / d, so the floor is exact for n < 10^6 (a full integer
+// division costs ~20 VALU per thread; the runs need three per tile or level)
+struct RcpDiv {
+    __device__ int operator()(int n, int d) const {
+        return (int)(((float)n + 0.5f) * __builtin_amdgcn_rcpf((float)d));
+    }
+};
+
+// The horizontal half: the four sums 16 D of one source row r for one quad.
+__device__ inline void rs_hsum(const uint8_t* r, int base, int4 sel, int4 cw, uint32_t D[4]) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(r + (base & ~3));
     const uint32_t sh = (uint32_t)(base & 3);
-    const uint32_t a0 = p0[0], a1 = p0[1], a2 = p0[2];
-    const uint32_t c0 = p1[0], c1 = p1[1], c2 = p1[2];
-    const uint32_t lo0 = __builtin_amdgcn_alignbyte(a1, a0, sh), hi0 = __builtin_amdgcn_alignbyte(a2, a1, sh);
-    const uint32_t lo1 = __builtin_amdgcn_alignbyte(c1, c0, sh), hi1 = __builtin_amdgcn_alignbyte(c2, c1, sh);
+    const uint32_t a0 = p[0], a1 = p[1], a2 = p[2];
+    const uint32_t lo = __builtin_amdgcn_alignbyte(a1, a0, sh), hi = __builtin_amdgcn_alignbyte(a2, a1, sh);
     const int sl[4] = {sel.x, sel.y, sel.z, sel.w};
     const int cl[4] = {cw.x, cw.y, cw.z, cw.w};
-    uint32_t D0[4], D1[4];  // 16 D
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t t0 = __builtin_amdgcn_perm(hi0, lo0, (uint32_t)sl[k]);
-        const uint32_t t1 = __builtin_amdgcn_perm(hi1, lo1, (uint32_t)sl[k]);
-        D0[k] = __builtin_amdgcn_udot2(as_u16x2(t0), as_u16x2((uint32_t)cl[k]), 0u, false);
-        D1[k] = __builtin_amdgcn_udot2(as_u16x2(t1), as_u16x2((uint32_t)cl[k]), 0u, false);
-    }
+    for (int k = 0; k < 4; ++k)
+        D[k] = __builtin_amdgcn_udot2(as_u16x2(__builtin_amdgcn_perm(hi, lo, (uint32_t)sl[k])),
+                                      as_u16x2((uint32_t)cl[k]), 0u, false);
+}
+
+// The vertical half: the quad's four output bytes from the sums of its two source rows.
+__device__ inline uint32_t rs_vert(const uint32_t D0[4], const uint32_t D1[4], int B0, int B1, int dx0, int simd_end) {
     uint32_t o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -149,8 +158,9 @@ __device__ inline BlurTile blur_tile(const BatchArgs& a, int t) {
 }
 
 // Window chunk i (16 bytes) of tile bt: rows reflected here (REFLECT_101), columns loaded as
-// they are (bounds-checked buffer load; chunks left of the plane are zero) -- the few column
-// bytes outside the plane that the taps reach are reflected in LDS afterwards (blur_fix_cols).
+// they are (bounds-checked buffer load; chunks left of the plane, or wholly beyond the 3 columns
+// the taps reach past its right edge, are zero and not loaded) -- the few column bytes outside the
+// plane that the taps reach are reflected in LDS afterwards (blur_tile_compute_mfma).
 template <int kAux = 0>
 __device__ inline uint4 blur_chunk(const BatchArgs& a, const BlurTile& bt, int i, int IWQ) {
     const LevelGeom G = a.lv[bt.l];
@@ -158,9 +168,12 @@ __device__ inline uint4 blur_chunk(const BatchArgs& a, const BlurTile& bt, int i
     // rows beyond the reflected range feed only zero weights or unwritten outputs: clamp
     const int y = min(max(refl101(bt.ty0 + r - 4, G.h), 0), G.h - 1);
     const int x = bt.tx0 - 16 + 16 * cq;
-    if (x < 0) return make_uint4(0, 0, 0, 0);
+    if (x < 0 || x >= G.w + 3) return make_uint4(0, 0, 0, 0);
+    // the range covers the dword that holds the plane's last byte whatever the row pitch's
+    // alignment (a dword that straddles the range's end reads as zero: the corner pixel of a level 0
+    // whose size is no multiple of 4); every buffer has that much room behind its last image
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)bt.src, (short)0, (int)min(G.img_stride, 0x7fffffffLL), 0x00020000);
+        (void*)bt.src, (short)0, (int)min(G.img_stride + 3, 0x7fffffffLL), 0x00020000);
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, y * G.pitch + x, 0, kAux);
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
@@ -230,57 +243,63 @@ __device__ inline void blur_tile_compute_mfma(const LevelGeom& G, int tx0, int t
         }
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n = lane & 31, h = lane >> 5;
     const uint8_t* wb = reinterpret_cast<const uint8_t*>(&tin4[0][0]);
-    auto ldc = [&](const uint32_t* p) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        return blur_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-    };
-    const blur_v4i B1[2] = {ldc(c_blur_mfma.b1[0][lane]), ldc(c_blur_mfma.b1[1][lane])};
-    const blur_v4i B2[2] = {ldc(c_blur_mfma.b2[0][lane]), ldc(c_blur_mfma.b2[1][lane])};
-    blur_v4i hi[2], lo[2];
-    const blur_v16i zero = {};
+    // a strip that starts at or beyond the plane's right edge holds no pixel (a level's last tile
+    // column: widths 533, 444, 370 fill 4.2, 3.5, 2.9 tiles): its wave skips both passes and the
+    // staging writes -- the store loop below never reads those columns of ob (x >= G.w), and the
+    // resize reads the raw window only -- and only joins the barriers
+    uint32_t* ob = reinterpret_cast<uint32_t*>(&hp[0][0]);  // output staging; hp is free: callers sync before reusing it
+    if (tx0 + 32 * w < G.w) {
+        auto ldc = [&](const uint32_t* p) {
+            const uint4 v = *reinterpret_cast<const uint4*>(p);
+            return blur_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+        };
+        const blur_v4i B1[2] = {ldc(c_blur_mfma.b1[0][lane]), ldc(c_blur_mfma.b1[1][lane])};
+        const blur_v4i B2[2] = {ldc(c_blur_mfma.b2[0][lane]), ldc(c_blur_mfma.b2[1][lane])};
+        blur_v4i hi[2], lo[2];
+        const blur_v16i zero = {};
 #pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-        const int row = min(32 * mb + n, IH - 1);
-        const uint8_t* src = wb + row * IW + 32 * w + 16 * h;
-        blur_v16i acc = zero;
+        for (int mb = 0; mb < 2; ++mb) {
+            const int row = min(32 * mb + n, IH - 1);
+            const uint8_t* src = wb + row * IW + 32 * w + 16 * h;
+            blur_v16i acc = zero;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const uint4 v = *reinterpret_cast<const uint4*>(src + 32 * k);
-            const blur_v4i a = {(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u),
-                                (int)(v.w ^ 0x80808080u)};
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, B1[k], acc, 0, 0, 0);
+            for (int k = 0; k < 2; ++k) {
+                const uint4 v = *reinterpret_cast<const uint4*>(src + 32 * k);
+                const blur_v4i a = {(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u),
+                                    (int)(v.w ^ 0x80808080u)};
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, B1[k], acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (mb == 1 && q > 0) {  // rows >= 40: no output row reads them; slot 4 carries the + 2^16
+                    hi[mb][q] = q == 1 ? 0x000000FF : 0;
+                    lo[mb][q] = 0;
+                    continue;
+                }
+                const uint32_t u0 = acc[4 * q], u1 = acc[4 * q + 1], u2 = acc[4 * q + 2], u3 = acc[4 * q + 3];
+                hi[mb][q] = (int)(__builtin_amdgcn_perm(u1, u0, 0x0c0c0501u) | (__builtin_amdgcn_perm(u3, u2, 0x0c0c0501u) << 16));
+                lo[mb][q] = (int)((__builtin_amdgcn_perm(u1, u0, 0x0c0c0400u) | (__builtin_amdgcn_perm(u3, u2, 0x0c0c0400u) << 16)) ^ 0x80808080u);
+            }
         }
+        blur_v16i ah = zero, al = zero;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(hi[mb], B2[mb], ah, 0, 0, 0);
+            al = __builtin_amdgcn_mfma_i32_32x32x32_i8(lo[mb], B2[mb], al, 0, 0, 0);
+        }
+        // output row n: columns 32w + 8q + 4h .. +3 from registers 4q .. 4q+3, staged row-major in LDS
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (mb == 1 && q > 0) {  // rows >= 40: no output row reads them; slot 4 carries the + 2^16
-                hi[mb][q] = q == 1 ? 0x000000FF : 0;
-                lo[mb][q] = 0;
-                continue;
-            }
-            const uint32_t u0 = acc[4 * q], u1 = acc[4 * q + 1], u2 = acc[4 * q + 2], u3 = acc[4 * q + 3];
-            hi[mb][q] = (int)(__builtin_amdgcn_perm(u1, u0, 0x0c0c0501u) | (__builtin_amdgcn_perm(u3, u2, 0x0c0c0501u) << 16));
-            lo[mb][q] = (int)((__builtin_amdgcn_perm(u1, u0, 0x0c0c0400u) | (__builtin_amdgcn_perm(u3, u2, 0x0c0c0400u) << 16)) ^ 0x80808080u);
+            uint32_t t4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t4[k] = ((uint32_t)ah[4 * q + k] << 8) + (uint32_t)al[4 * q + k];
+            const uint32_t packed = (__builtin_amdgcn_perm(t4[1], t4[0], 0x0c0c0602u) |
+                                     (__builtin_amdgcn_perm(t4[3], t4[2], 0x0c0c0602u) << 16)) ^ 0x80808080u;
+            ob[n * (OP / 4) + 8 * w + 2 * q + h] = packed;
         }
-    }
-    blur_v16i ah = zero, al = zero;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-        ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(hi[mb], B2[mb], ah, 0, 0, 0);
-        al = __builtin_amdgcn_mfma_i32_32x32x32_i8(lo[mb], B2[mb], al, 0, 0, 0);
-    }
-    // output row n: columns 32w + 8q + 4h .. +3 from registers 4q .. 4q+3, staged row-major in LDS
-    uint32_t* ob = reinterpret_cast<uint32_t*>(&hp[0][0]);  // hp is free: callers sync before reusing it
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t t4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t4[k] = ((uint32_t)ah[4 * q + k] << 8) + (uint32_t)al[4 * q + k];
-        const uint32_t packed = (__builtin_amdgcn_perm(t4[1], t4[0], 0x0c0c0602u) |
-                                 (__builtin_amdgcn_perm(t4[3], t4[2], 0x0c0c0602u) << 16)) ^ 0x80808080u;
-        ob[n * (OP / 4) + 8 * w + 2 * q + h] = packed;
     }
     __syncthreads();
     // stores as the VALU path: thread -> column quad cq, rows R rg .. R rg + R - 1
@@ -361,11 +380,12 @@ hipError_t launch_blur_level(const BatchArgs& a, int l, hipStream_t s) {
 // second read of level l - 1 and the blur of level l - 1 none of its own.  Ownership tables
 // (band_row / tile_quad) come from the host with the resize coefficients.
 static_assert(kBrMaxQuads >= kBlurTW / 4 + 1 && kBrMaxRows >= kBlurTH + 1, "ownership caps");
+static_assert(kBrMaxQuads <= 64 && kBrMaxRows <= 64, "br_tile copies each table with one wave");
 
 struct BrSmem {
     uint4 tin4[kBlurTH + 8][(kBlurTW + 32) / 16];
     uint4 hp[(kBlurTH + 8) / 2][kBlurTW / 4];
-    // per owned output quad (rs_quad): tap selectors, coefficient pairs, first left tap; one
+    // per owned output quad (rs_hsum): tap selectors, coefficient pairs, first left tap; one
     // array per field so a wave's consecutive quads read consecutive entries
     int4 xsel[kBrMaxQuads];
     int4 xcw[kBrMaxQuads];
@@ -403,25 +423,15 @@ __device__ inline void br_tile(const BatchArgs& a, int l, bool resize, int img, 
         nr = min(band_row[by + 1] - r0, kBrMaxRows);
         nq = min(tile_quad[bx + 1] - q0, kBrMaxQuads);
         if (!G.area2) {
-            if (threadIdx.x < nq) {
-                const int q = threadIdx.x;
-                int4 x[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) x[k] = a.rtab[G.xtab_off + min(4 * (q0 + q) + k, G.w - 1)];
-                const int base = x[0].x;
-                int sl[4], cl[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {  // taps relative to base: 0 .. 7 (scale <= 2)
-                    sl[k] = (x[k].x - base) | 0x0c00 | ((x[k].y - base) << 16) | 0x0c000000;
-                    cl[k] = (x[k].z << 4) | (x[k].w << 20);  // 16 c (rs_quad)
-                }
-                sm.xsel[q] = make_int4(sl[0], sl[1], sl[2], sl[3]);
-                sm.xcw[q] = make_int4(cl[0], cl[1], cl[2], cl[3]);
-                sm.xbase[q] = base;
-            }
-            if (threadIdx.x < nr) {  // (y0, y1, b0 << 8, b1 << 8): rs_quad's v_mul_hi_u32_u24 operands
-                const int4 y = a.rtab[G.ytab_off + r0 + threadIdx.x];
-                sm.yts[threadIdx.x] = make_int4(y.x, y.y, y.z << 8, y.w << 8);
+            // the host's finished records (orb_geometry.h resize_level), copied as they are: one
+            // field per wave, so no wave carries more than one load and one LDS store to the barrier
+            const int f = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), i = threadIdx.x & 63;
+            if (f < 2) {
+                if (i < nq) (f ? sm.xcw : sm.xsel)[i] = a.rtab[G.qrec_off + 2 * (q0 + i) + f];
+            } else if (f == 2) {
+                if (i < nq) sm.xbase[i] = reinterpret_cast<const int*>(a.rtab)[G.qbase_off + q0 + i];
+            } else if (i < nr) {
+                sm.yts[i] = a.rtab[G.yrec_off + r0 + i];
             }
         }
     }
@@ -437,19 +447,15 @@ __device__ inline void br_tile(const BatchArgs& a, int l, bool resize, int img, 
     const uint8_t* wb = reinterpret_cast<const uint8_t*>(&sm.tin4[0][0]);
     const int wy0 = bt.ty0 - 4, wx0 = bt.tx0 - 16;
     uint8_t* dst = a.lvl_base[l] + (long long)img * G.img_stride;
-    // thread -> (quad q, rows rr0, rr0 + step, ...): the quad's selectors and coefficients are
-    // read once per tile, one division per tile instead of one per output quad
+    // thread -> (quad q, the run of consecutive owned rows [row0, row1)) (resize_run): the quad's
+    // selectors and coefficients are read once per tile, and inside the run a source row that two
+    // output rows share has its sums formed once
     if (nq <= 0) return;
-    // t / nq and 256 / nq by v_rcp_f32 (1 ulp): (t + 0.5) / nq for t <= 256, nq <= kBrMaxQuads
-    // lies >= 0.5 / nq from an integer, far beyond the error, so the floors are exact (a full
-    // integer division here cost ~20 VALU per thread and tile)
-    const float rnq = __builtin_amdgcn_rcpf((float)nq);
-    const int step = max((int)(256.5f * rnq), 1);
-    const int rr0 = (int)(((float)threadIdx.x + 0.5f) * rnq), q = (int)threadIdx.x - rr0 * nq;
-    if (rr0 >= step) return;
+    const ResizeRun run = resize_run((int)threadIdx.x, nq, nr, 256, RcpDiv{});
+    const int q = run.q;
     const int dx0 = 4 * (q0 + q);
     if (G.area2) {
-        for (int rr = rr0; rr < nr; rr += step) {
+        for (int rr = run.row0; rr < run.row1; ++rr) {
             const int dy = r0 + rr;
             const uint8_t* s0 = wb + __mul24(2 * dy - wy0, IW) - wx0;
             const uint8_t* s1 = s0 + IW;
@@ -463,15 +469,27 @@ __device__ inline void br_tile(const BatchArgs& a, int l, bool resize, int img, 
             *reinterpret_cast<uint32_t*>(dst + plane_off(dy, G.pitch, dx0)) = packed;
         }
     } else {
+        if (run.row0 >= run.row1) return;
         const int4 xsel = sm.xsel[q], xcw = sm.xcw[q];
         const int xbase = sm.xbase[q];
-        for (int rr = rr0; rr < nr; rr += step) {
-            const int dy = r0 + rr;
+        const int woff = -__mul24(wy0, IW) - wx0;  // window byte offset of source (row 0, column 0)
+        int carried = -1;  // the source row whose sums the previous output row left behind
+        // one output row: F holds the first source row's sums (the previous row's S when that row
+        // is carried), S takes the second one's; two steps per trip with the sets swapped, so the
+        // carried sums never move between registers
+        auto step = [&](uint32_t (&F)[4], uint32_t (&S)[4], int rr) {
             const int4 yt = sm.yts[rr];
-            const uint8_t* row0 = wb + __mul24(yt.x - wy0, IW) - wx0;
-            const uint8_t* row1 = wb + __mul24(yt.y - wy0, IW) - wx0;
-            const uint32_t packed = rs_quad(row0, row1, xbase, xsel, xcw, yt.z, yt.w, dx0, G.simd_end);
-            *reinterpret_cast<uint32_t*>(dst + plane_off(dy, G.pitch, dx0)) = packed;
+            if (!resize_row_carried(carried, yt.x)) rs_hsum(wb + (woff + __mul24(yt.x, IW)), xbase, xsel, xcw, F);
+            rs_hsum(wb + (woff + __mul24(yt.y, IW)), xbase, xsel, xcw, S);
+            carried = yt.y;
+            *reinterpret_cast<uint32_t*>(dst + plane_off(r0 + rr, G.pitch, dx0)) = rs_vert(F, S, yt.z, yt.w, dx0, G.simd_end);
+        };
+        uint32_t Da[4], Db[4];
+        for (int rr = run.row0;;) {
+            step(Da, Db, rr);
+            if (++rr >= run.row1) break;
+            step(Db, Da, rr);
+            if (++rr >= run.row1) break;
         }
     }
 }
@@ -497,7 +515,7 @@ __global__ __launch_bounds__(256) void k_blur_resize(BatchArgs a, int l, uint32_
 // k_level_linear: level l from level l - 1 in HBM for any scale step (ComputePyramid's cv::resize
 // INTER_LINEAR, ORBextractor_old.cc:1342-1344; the generic 2-tap path of OpenCV 4.2's resize, as
 // oracle/orb_oracle.cpp resize_linear restates it).  k_blur_resize stages one blur tile of level
-// l - 1 and makes the outputs whose taps it holds, which needs scale steps <= 2 (rs_quad reads the
+// l - 1 and makes the outputs whose taps it holds, which needs scale steps <= 2 (rs_hsum reads the
 // 8 source bytes from a quad's first tap); scale factors above 2 (accepted by ORBextractor, not
 // used by ORB-SLAM3's configurations) take this kernel and then k_blur per level.  Thread = one
 // output quad of one row; every tap is a byte load from the previous level.
@@ -558,7 +576,7 @@ hipError_t launch_blur_resize(const BatchArgs& a, int l, hipStream_t s) {
 // for 24 K pixels per image).  Two buffers alternate (level s0 + 2k in buffer 0, s0 + 2k + 1 in
 // buffer 1; each level is smaller than the one two steps before).  Row pitch Pitch(l) holds kTailPad
 // bytes on the left (REFLECT_101 columns -3 .. -1) and >= 12 on the right (resize reads 12
-// bytes from a quad's first tap), so the blur and rs_quad read the same window layout as k_blur.
+// bytes from a quad's first tap), so the blur and rs_hsum read the same window layout as k_blur.
 constexpr int kTailThreads = 1024;
 
 __device__ inline void tail_fill_pads(uint8_t* buf, int P, int w, int h) {
@@ -691,25 +709,14 @@ __global__ __launch_bounds__(kTailThreads) void k_pyr_tail(BatchArgs a) {
         const LevelGeom G = a.lv[resize ? s + 1 : s];
         const int nq = (G.w + 3) >> 2;
         if (resize && !G.area2) {  // level s + 1's quad and row coefficients (as br_tile)
-            for (int q = threadIdx.x; q < nq; q += kTailThreads) {
-                int4 xx[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) xx[k] = a.rtab[G.xtab_off + min(4 * q + k, G.w - 1)];
-                const int base = xx[0].x;
-                int sl[4], cl[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    sl[k] = (xx[k].x - base) | 0x0c00 | ((xx[k].y - base) << 16) | 0x0c000000;
-                    cl[k] = (xx[k].z << 4) | (xx[k].w << 20);
-                }
-                xsel[q] = make_int4(sl[0], sl[1], sl[2], sl[3]);
-                xcw[q] = make_int4(cl[0], cl[1], cl[2], cl[3]);
-                xbase[q] = base;
+            // the host's finished records, copied as they are: the x fields from the workgroup's
+            // first threads, the rows from its last ones (other waves: they overlap)
+            for (int i = threadIdx.x; i < 2 * nq; i += kTailThreads) {
+                const int q = i >> 1;
+                ((i & 1) ? xcw : xsel)[q] = a.rtab[G.qrec_off + i];
+                if (!(i & 1)) xbase[q] = reinterpret_cast<const int*>(a.rtab)[G.qbase_off + q];
             }
-            for (int r = threadIdx.x; r < G.h; r += kTailThreads) {
-                const int4 y = a.rtab[G.ytab_off + r];
-                yts[r] = make_int4(y.x, y.y, y.z << 8, y.w << 8);
-            }
+            for (int r = kTailThreads - 1 - (int)threadIdx.x; r < G.h; r += kTailThreads) yts[r] = a.rtab[G.yrec_off + r];
         }
         tail_blur(cur, S.tpitch, S, a.blur_base[s] + (long long)img * S.bimg_stride);
         if (!resize) break;
@@ -717,28 +724,44 @@ __global__ __launch_bounds__(kTailThreads) void k_pyr_tail(BatchArgs a) {
         uint8_t* nxt = buf((s + 1 - s0) & 1);
         uint8_t* dst = a.lvl_base[s + 1] + (long long)img * G.img_stride;
         const uint8_t* rowp = cur + kTailPad;
-        // thread -> (quad q, rows dy0, dy0 + step, ...): one division per level
-        const int step = max(kTailThreads / nq, 1);
-        const int q = (int)threadIdx.x % nq, dyt = (int)threadIdx.x / nq;
-        for (int dy = dyt; dy < G.h && dyt < step; dy += step) {
-            const int dx0 = 4 * q;
-            uint32_t packed = 0;
-            if (G.area2) {
+        // thread -> (quad q, the run of consecutive rows [row0, row1)) as br_tile (resize_run)
+        const ResizeRun run = resize_run((int)threadIdx.x, nq, G.h, kTailThreads, RcpDiv{});
+        const int q = run.q, dx0 = 4 * q;
+        auto put = [&](int dy, uint32_t packed) {
+            *reinterpret_cast<uint32_t*>(nxt + __mul24(dy, G.tpitch) + kTailPad + dx0) = packed;
+            *reinterpret_cast<uint32_t*>(dst + plane_off(dy, G.pitch, dx0)) = packed;
+        };
+        if (G.area2) {
+            for (int dy = run.row0; dy < run.row1; ++dy) {
                 const uint8_t* s0r = rowp + __mul24(2 * dy, S.tpitch);
                 const uint8_t* s1r = s0r + S.tpitch;
+                uint32_t packed = 0;
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                     const int dx = min(dx0 + kk, G.w - 1);
                     const int o = (s0r[2 * dx] + s0r[2 * dx + 1] + s1r[2 * dx] + s1r[2 * dx + 1] + 2) >> 2;
                     packed |= (uint32_t)o << (8 * kk);
                 }
-            } else {
-                const int4 yt = yts[dy];
-                packed = rs_quad(rowp + __mul24(yt.x, S.tpitch), rowp + __mul24(yt.y, S.tpitch), xbase[q], xsel[q],
-                                 xcw[q], yt.z, yt.w, dx0, G.simd_end);
+                put(dy, packed);
             }
-            *reinterpret_cast<uint32_t*>(nxt + __mul24(dy, G.tpitch) + kTailPad + dx0) = packed;
-            *reinterpret_cast<uint32_t*>(dst + plane_off(dy, G.pitch, dx0)) = packed;
+        } else if (run.row0 < run.row1) {
+            const int4 qsel = xsel[q], qcw = xcw[q];
+            const int qbase = xbase[q];
+            int carried = -1;
+            auto step = [&](uint32_t (&F)[4], uint32_t (&Sn)[4], int dy) {  // br_tile's step
+                const int4 yt = yts[dy];
+                if (!resize_row_carried(carried, yt.x)) rs_hsum(rowp + __mul24(yt.x, S.tpitch), qbase, qsel, qcw, F);
+                rs_hsum(rowp + __mul24(yt.y, S.tpitch), qbase, qsel, qcw, Sn);
+                carried = yt.y;
+                put(dy, rs_vert(F, Sn, yt.z, yt.w, dx0, G.simd_end));
+            };
+            uint32_t Da[4], Db[4];
+            for (int dy = run.row0;;) {
+                step(Da, Db, dy);
+                if (++dy >= run.row1) break;
+                step(Db, Da, dy);
+                if (++dy >= run.row1) break;
+            }
         }
         __syncthreads();  // level s + 1 complete in LDS; level s's buffer and the tables are free
         tail_fill_pads(nxt, G.tpitch, G.w, G.h);
