@@ -246,9 +246,7 @@ def sort_nodes(size, ulx):
     return perm
 
 
-def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor=1.2):
-    """Frame::ComputeStereoMatches (Frame.cc:827-997) -> (mvuRight, mvDepth, sad) float32/int32.
-    pyr_l / pyr_r: the unblurred pyramids (lists of levels, as pyramid() returns)."""
+def _stereo_call(coded, kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor):
     nlevels = len(pyr_l)
     kl = np.ascontiguousarray(kps_l, dtype=KP_DTYPE)
     kr = np.ascontiguousarray(kps_r, dtype=KP_DTYPE)
@@ -265,10 +263,35 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_fa
     ur = np.zeros(n, np.float32)
     dep = np.zeros(n, np.float32)
     sad = np.zeros(n, np.int32)
-    lib().oracle_stereo_matches(_p(kl), n, _p(dl), _p(kr), len(kr), _p(dr), PL, PR, _p(lw), _p(lh),
-                                nlevels, _p(scale), _p(inv_scale), C.c_float(mbf), C.c_float(mb),
-                                _p(ur), _p(dep), _p(sad))
-    return ur, dep, sad
+    args = [_p(kl), n, _p(dl), _p(kr), len(kr), _p(dr), PL, PR, _p(lw), _p(lh), nlevels, _p(scale),
+            _p(inv_scale), C.c_float(mbf), C.c_float(mb), _p(ur), _p(dep), _p(sad)]
+    if not coded:
+        lib().oracle_stereo_matches(*args)
+        return ur, dep, sad
+    code = np.zeros(n, np.int32)
+    flags = np.zeros(n, np.int32)
+    lib().oracle_stereo_matches_coded(*args, _p(code), _p(flags))
+    return ur, dep, sad, code, flags
+
+
+def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor=1.2):
+    """Frame::ComputeStereoMatches (Frame.cc:827-997) -> (mvuRight, mvDepth, sad) float32/int32.
+    pyr_l / pyr_r: the unblurred pyramids (lists of levels, as pyramid() returns)."""
+    return _stereo_call(False, kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor)
+
+
+# decision codes / flags of stereo_matches_coded (ORACLE_STEREO_* in orb_oracle.h)
+(ST_ROW_RANGE, ST_ROW_EMPTY, ST_MAXU, ST_NO_CANDIDATE, ST_HAMMING, ST_INIU_ENDU, ST_WINDOW, ST_BORDER_SHIFT,
+ ST_DELTA, ST_DISPARITY_NEG, ST_DISPARITY_MAX, ST_ACCEPTED, ST_ACCEPTED_ZERO, ST_MEDIAN) = range(1, 15)
+(STF_HAMMING_TIE, STF_SAD_TIE, STF_OCTAVE_GATE, STF_NEIGHBOUR_OCTAVE, STF_SAD_HIGH, STF_ZERO_BRANCH,
+ STF_BAND_EDGE) = 1, 2, 4, 8, 16, 32, 64
+
+
+def stereo_matches_coded(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor=1.2):
+    """stereo_matches() plus, per left keypoint, the first rule that stopped the row (code, ST_*;
+    ST_ACCEPTED / ST_ACCEPTED_ZERO = kept, ST_MEDIAN = accepted, then rejected by the median rule)
+    and what it met on the way (flags, STF_*) -> (mvuRight, mvDepth, sad, code, flags)."""
+    return _stereo_call(True, kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, mbf, mb, scale_factor)
 
 
 def fisheye_stereo(kps_l, mono_l, kps_r, mono_r, idx1, dist1, rig, sigma2):

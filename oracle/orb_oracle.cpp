@@ -1002,13 +1002,29 @@ void oracle_sort_nodes(const int32_t* size, const int32_t* ulx, int n, int32_t* 
 // Writes mvuRight / mvDepth (-1 = no stereo match) and, for tests, the SAD distance of each
 // accepted match in sad[] (-1 otherwise; entries later rejected by the median rule keep theirs).
 // Float expressions are evaluated in source order without contraction (-ffp-contract=off).
-void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, const oracle_kp* kpsR,
-                           int nR, const uint8_t* descR, const uint8_t* const* pyrL,
-                           const uint8_t* const* pyrR, const int* lw, const int* lh, int nlevels,
-                           const float* scale, const float* inv_scale, float mbf, float mb,
-                           float* uRight, float* depth, int32_t* sad) {
-    (void)nlevels;
+//
+// code / flags (optional, one per left keypoint; for tests): code = the first rule that stops the
+// row, in source order (ORACLE_STEREO_* in orb_oracle.h): 1 row out of table, 2 empty row list,
+// 3 maxU < 0, 4 no candidate passes the octave and [minU, maxU] gates, 5 best Hamming distance >=
+// 75, 6 iniu / endu, 7 the added window guards, 8 bestincR == +-5, 9 deltaR out of range,
+// 10 disparity < 0, 11 disparity >= maxD, 12 accepted, 13 accepted through the disparity <= 0
+// branch, 14 accepted (12 or 13) and then rejected by the median rule; a 12 or 13 that remains was
+// kept.  flags: 1 two or more gated candidates share the best Hamming distance, 2 the SAD minimum
+// is attained at two or more shifts, 4 an in-range candidate was dropped by the octave gate, 8 the
+// best candidate is in a neighbouring octave, 16 some SAD of the row's 11 shifts is >= 16384,
+// 32 the row went through the disparity <= 0 branch (it survives code 14), 64 the best candidate
+// (Hamming distance < 75) has floor(y) exactly ceil(2 scale[min(levelL + 1, nlevels - 1)]) + 1 rows
+// from the left row: the outermost row a band search around the left row has to visit.
+static void stereo_matches_impl(const oracle_kp* kpsL, int nL, const uint8_t* descL, const oracle_kp* kpsR,
+                                int nR, const uint8_t* descR, const uint8_t* const* pyrL,
+                                const uint8_t* const* pyrR, const int* lw, const int* lh, int nlevels,
+                                const float* scale, const float* inv_scale, float mbf, float mb,
+                                float* uRight, float* depth, int32_t* sad, int32_t* code, int32_t* flags) {
     for (int i = 0; i < nL; ++i) uRight[i] = -1.0f, depth[i] = -1.0f, sad[i] = -1;
+    std::vector<int32_t> codeTmp, flagsTmp;
+    if (!code) codeTmp.resize(nL > 0 ? nL : 1), code = codeTmp.data();
+    if (!flags) flagsTmp.resize(nL > 0 ? nL : 1), flags = flagsTmp.data();
+    for (int i = 0; i < nL; ++i) code[i] = 0, flags[i] = 0;
     const int TH_HIGH = 100, TH_LOW = 50;       // ORBmatcher.cc:36-37
     const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
     const int nRows = lh[0];
@@ -1034,29 +1050,47 @@ void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, 
         const float& vL = kpL.y;
         const float& uL = kpL.x;
         const size_t row = (size_t)vL;
+        code[iL] = ORACLE_STEREO_ROW_RANGE;
         if (row >= (size_t)nRows) continue;
         const std::vector<size_t>& vCandidates = vRowIndices[row];
+        code[iL] = ORACLE_STEREO_ROW_EMPTY;
         if (vCandidates.empty()) continue;
         const float minU = uL - maxD;
         const float maxU = uL - minD;
+        code[iL] = ORACLE_STEREO_MAXU;
         if (maxU < 0) continue;
         int bestDist = TH_HIGH;
         size_t bestIdxR = 0;
+        int nGated = 0, nAtBest = 0;
         const uint8_t* dL = descL + 32 * (size_t)iL;
         for (size_t iC = 0; iC < vCandidates.size(); iC++) {
             const size_t iR = vCandidates[iC];
             const oracle_kp& kpR = kpsR[iR];
-            if (kpR.octave < levelL - 1 || kpR.octave > levelL + 1) continue;
+            if (kpR.octave < levelL - 1 || kpR.octave > levelL + 1) {
+                if (kpR.x >= minU && kpR.x <= maxU) flags[iL] |= ORACLE_STEREO_F_OCTAVE_GATE;
+                continue;
+            }
             const float& uR = kpR.x;
             if (uR >= minU && uR <= maxU) {
                 const int dist = oracle_descriptor_distance(dL, descR + 32 * iR);
+                ++nGated;
+                if (dist == bestDist) ++nAtBest;
                 if (dist < bestDist) {
                     bestDist = dist;
                     bestIdxR = iR;
+                    nAtBest = 1;
                 }
             }
         }
+        if (bestDist < TH_HIGH) {
+            if (nAtBest >= 2) flags[iL] |= ORACLE_STEREO_F_HAMMING_TIE;
+            if (kpsR[bestIdxR].octave != levelL) flags[iL] |= ORACLE_STEREO_F_NEIGHBOUR_OCTAVE;
+        }
+        code[iL] = nGated == 0 ? ORACLE_STEREO_NO_CANDIDATE : ORACLE_STEREO_HAMMING;
         if (bestDist < thOrbDist) {
+            const int omax = levelL + 1 < nlevels ? levelL + 1 : nlevels - 1;
+            if (std::abs((int)std::floor(kpsR[bestIdxR].y) - (int)row) == (int)std::ceil(2.0f * scale[omax]) + 1)
+                flags[iL] |= ORACLE_STEREO_F_BAND_EDGE;
             const float uR0 = kpsR[bestIdxR].x;
             const float scaleFactor = inv_scale[kpL.octave];
             const float scaleduL = std::round(kpL.x * scaleFactor);
@@ -1071,8 +1105,10 @@ void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, 
             float vDists[2 * L + 1];
             const float iniu = scaleduR0 + L - w;
             const float endu = scaleduR0 + L + w + 1;
+            code[iL] = ORACLE_STEREO_INIU_ENDU;
             if (iniu < 0 || endu >= W) continue;
             // cv::Mat rowRange/colRange would assert outside the level; never reached here
+            code[iL] = ORACLE_STEREO_WINDOW;
             if (r0 < 0 || r0 + 2 * w + 1 > H || c0 < 0 || c0 + 2 * w + 1 > W || (int)scaleduR0 - L - w < 0) continue;
             for (int incR = -L; incR <= +L; incR++) {
                 const int cr = (int)scaleduR0 + incR - w;
@@ -1088,18 +1124,30 @@ void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, 
                 }
                 vDists[L + incR] = dist;
             }
+            int nAtMin = 0;
+            for (int k = 0; k < 2 * L + 1; ++k) {
+                if (vDists[k] == (float)sadBest) ++nAtMin;
+                if (vDists[k] >= 16384.0f) flags[iL] |= ORACLE_STEREO_F_SAD_HIGH;
+            }
+            if (nAtMin >= 2) flags[iL] |= ORACLE_STEREO_F_SAD_TIE;
+            code[iL] = ORACLE_STEREO_BORDER_SHIFT;
             if (bestincR == -L || bestincR == L) continue;
             const float dist1 = vDists[L + bestincR - 1];
             const float dist2 = vDists[L + bestincR];
             const float dist3 = vDists[L + bestincR + 1];
             const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
+            code[iL] = ORACLE_STEREO_DELTA;
             if (deltaR < -1 || deltaR > 1) continue;
             float bestuR = scale[kpL.octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
             float disparity = (uL - bestuR);
+            code[iL] = disparity >= minD ? ORACLE_STEREO_DISPARITY_MAX : ORACLE_STEREO_DISPARITY_NEG;
             if (disparity >= minD && disparity < maxD) {
+                code[iL] = ORACLE_STEREO_ACCEPTED;
                 if (disparity <= 0) {
                     disparity = 0.01;
                     bestuR = uL - 0.01;
+                    code[iL] = ORACLE_STEREO_ACCEPTED_ZERO;
+                    flags[iL] |= ORACLE_STEREO_F_ZERO_BRANCH;
                 }
                 depth[iL] = mbf / disparity;
                 uRight[iL] = bestuR;
@@ -1118,8 +1166,28 @@ void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, 
         else {
             uRight[vDistIdx[i].second] = -1;
             depth[vDistIdx[i].second] = -1;
+            code[vDistIdx[i].second] = ORACLE_STEREO_MEDIAN;
         }
     }
+}
+
+extern "C" void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, const oracle_kp* kpsR,
+                                      int nR, const uint8_t* descR, const uint8_t* const* pyrL,
+                                      const uint8_t* const* pyrR, const int* lw, const int* lh, int nlevels,
+                                      const float* scale, const float* inv_scale, float mbf, float mb,
+                                      float* uRight, float* depth, int32_t* sad) {
+    stereo_matches_impl(kpsL, nL, descL, kpsR, nR, descR, pyrL, pyrR, lw, lh, nlevels, scale, inv_scale, mbf, mb, uRight,
+                        depth, sad, nullptr, nullptr);
+}
+
+extern "C" void oracle_stereo_matches_coded(const oracle_kp* kpsL, int nL, const uint8_t* descL,
+                                            const oracle_kp* kpsR, int nR, const uint8_t* descR,
+                                            const uint8_t* const* pyrL, const uint8_t* const* pyrR, const int* lw,
+                                            const int* lh, int nlevels, const float* scale, const float* inv_scale,
+                                            float mbf, float mb, float* uRight, float* depth, int32_t* sad,
+                                            int32_t* code, int32_t* flags) {
+    stereo_matches_impl(kpsL, nL, descL, kpsR, nR, descR, pyrL, pyrR, lw, lh, nlevels, scale, inv_scale, mbf, mb, uRight,
+                        depth, sad, code, flags);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -112,6 +112,38 @@ void oracle_stereo_matches(const oracle_kp* kpsL, int nL, const uint8_t* descL, 
                            const uint8_t* const* pyrR, const int* lw, const int* lh, int nlevels,
                            const float* scale, const float* inv_scale, float mbf, float mb,
                            float* uRight, float* depth, int32_t* sad);
+// The same call (uRight / depth / sad byte-identical) that also reports, per left keypoint, the
+// first rule that stopped the row (code, in source order) and what the row met on the way (flags).
+enum {
+    ORACLE_STEREO_ROW_RANGE = 1,       // (size_t)vL outside the row table
+    ORACLE_STEREO_ROW_EMPTY = 2,       // vRowIndices[vL] empty
+    ORACLE_STEREO_MAXU = 3,            // maxU < 0
+    ORACLE_STEREO_NO_CANDIDATE = 4,    // no candidate passes the octave and [minU, maxU] gates
+    ORACLE_STEREO_HAMMING = 5,         // best Hamming distance >= (TH_HIGH + TH_LOW) / 2
+    ORACLE_STEREO_INIU_ENDU = 6,       // iniu < 0 || endu >= cols
+    ORACLE_STEREO_WINDOW = 7,          // the window guards added to the reference's
+    ORACLE_STEREO_BORDER_SHIFT = 8,    // bestincR == -L || bestincR == L
+    ORACLE_STEREO_DELTA = 9,           // deltaR outside [-1, 1]
+    ORACLE_STEREO_DISPARITY_NEG = 10,  // disparity < minD
+    ORACLE_STEREO_DISPARITY_MAX = 11,  // disparity >= maxD
+    ORACLE_STEREO_ACCEPTED = 12,       // accepted and kept by the median rule
+    ORACLE_STEREO_ACCEPTED_ZERO = 13,  // accepted through the disparity <= 0 branch, and kept
+    ORACLE_STEREO_MEDIAN = 14          // accepted (12 or 13), then rejected by the median rule
+};
+enum {
+    ORACLE_STEREO_F_HAMMING_TIE = 1,       // two or more gated candidates share the best distance
+    ORACLE_STEREO_F_SAD_TIE = 2,           // the SAD minimum is attained at two or more shifts
+    ORACLE_STEREO_F_OCTAVE_GATE = 4,       // a candidate inside [minU, maxU] dropped by the octave gate
+    ORACLE_STEREO_F_NEIGHBOUR_OCTAVE = 8,  // the best candidate's octave differs from the left one's
+    ORACLE_STEREO_F_SAD_HIGH = 16,         // one of the row's 11 SADs is >= 16384
+    ORACLE_STEREO_F_ZERO_BRANCH = 32,      // went through the disparity <= 0 branch (kept under code 14)
+    ORACLE_STEREO_F_BAND_EDGE = 64         // the best candidate (< 75) lies ceil(2 scale[omax]) + 1 rows away
+};
+void oracle_stereo_matches_coded(const oracle_kp* kpsL, int nL, const uint8_t* descL, const oracle_kp* kpsR,
+                                 int nR, const uint8_t* descR, const uint8_t* const* pyrL,
+                                 const uint8_t* const* pyrR, const int* lw, const int* lh, int nlevels,
+                                 const float* scale, const float* inv_scale, float mbf, float mb,
+                                 float* uRight, float* depth, int32_t* sad, int32_t* code, int32_t* flags);
 
 // Frame::UndistortKeyPoints (Frame.cc:763-796; cv::undistortPoints, 5 fixed-point iterations in
 // double, P = K), Frame::ComputeImageBounds (:798-825) and Frame::AssignFeaturesToGrid +

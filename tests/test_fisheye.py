@@ -173,3 +173,99 @@ def test_fisheye_stereo_batch_matches_oracle(oracle, rig_kind):
         total_rej += int(((r["code"] >= 4) & (r["code"] <= 9)).sum())
     print("fisheye %s: accepted %d rejected %d, bit-exact" % (rig_kind, total_acc, total_rej))
     assert total_acc > 100 and total_rej > 0, (total_acc, total_rej)
+
+
+# ---------------------------------------------------------------------------------------------
+# Every decision code of ComputeStereoFishEyeMatches / TriangulateMatches, one by one: three right
+# eyes x a handful of rigs at 320 x 240 (the intrinsics above, halved).
+CAM_L2 = [v / 2 for v in CAM_L[:4]] + CAM_L[4:]
+CAM_R2 = [v / 2 for v in CAM_R[:4]] + CAM_R[4:]
+REACH_RIGS = [  # name, R12, t12
+    ("nominal", np.eye(3), (0.12, 0.0, 0.0)),
+    ("reversed", np.eye(3), (-0.12, 0.0, 0.0)),                # z1 <= 0 for the true matches
+    ("vertical", np.eye(3), (0.0, 0.12, 0.0)),
+    ("tiny", np.eye(3), (5e-6, 0.0, 0.0)),                     # depths below 1e-4
+    ("rot_x", _rot(0.04, 0.0, 0.0), (0.12, 0.0, 0.0)),
+    ("rot_y", _rot(0.0, 0.05, 0.0), (0.12, 0.0, 0.0)),
+    ("rot_y_neg", _rot(0.0, -0.03, 0.0), (0.12, 0.0, 0.0)),
+    ("small", _rot(0.004, -0.006, 0.002), (0.12, 0.003, -0.002)),
+    ("backwards", _rot(0.0, np.pi, 0.0), (0.12, 0.0, 0.0)),    # the second camera looks backwards: z2 <= 0
+    ("forward", np.eye(3), (0.0, 0.0, 3.0)),                   # the second camera far forward: z2 <= 0
+]
+# Rows per code over the 3 x 10 combinations, at least [measured on the CPU oracle].  Code 3 (index
+# out of range) is asserted to be 0: the kNN2 returns a train row of the same stereo block or
+# nothing (dist1 = 0x7fff..., code 2), never an out-of-range row.  Code 6 (z2 <= 0), seen once
+# with the natural rigs, is reached by the backwards and forward rigs.
+REACH_MINIMA = {1: (10, 10530), 2: (10, 1590), 4: (10, 1225), 5: (10, 6545), 6: (1, 1061), 7: (10, 1200),
+                8: (1, 41), 9: (10, 739), 10: (10, 7219)}
+
+
+def _reach_eyes():
+    """(name, left, right): the 12-px pair, a noisy copy (+-8) and an exact copy of the left eye."""
+    L, R = synth.stereo_pair(240, 320, 21)
+    noise = np.random.default_rng(3).integers(-8, 9, L.shape)
+    noisy = np.clip(L.astype(np.int64) + noise, 0, 255).astype(np.uint8)
+    return [("pair12", L, R), ("noisy", L, noisy), ("copy", L, L.copy())]
+
+
+def _reach_rig(R12, t12):
+    return dict(cam_left=CAM_L2, cam_right=CAM_R2, R12=np.asarray(R12, np.float32), t12=list(t12),
+                precision_left=1e-6, precision_right=1e-6)
+
+
+def test_rigs_reach_every_rejection_code(oracle):
+    """Counts rows per decision code over the eyes and rigs the GPU test below runs."""
+    rows = np.zeros(11, np.int64)
+    near = 0
+    for _, L, R in _reach_eyes():
+        kl, dl, ml = oracle.extract(L, nfeatures=1000, lap=(0, 320))
+        kr, dr, mr = oracle.extract(R, nfeatures=1000, lap=(0, 320))
+        i1, d1, _, _ = oracle.knn2(dl[ml:], dr[mr:])
+        assert len(kl) - ml > 500 and len(kr) - mr > 500
+        for _, R12, t12 in REACH_RIGS:
+            r = oracle.fisheye_stereo(kl, ml, kr, mr, i1, d1, _reach_rig(R12, t12), _sigma2())
+            rows += np.bincount(r["code"], minlength=11)
+            assert r["n_matches"] == (r["code"] == 10).sum() == (r["l2r"] >= 0).sum()
+            near += sum(_near(m, c) for m, c in zip(r["margins"], r["code"]))
+    print("fisheye rows per code 0..10:", rows.tolist(), "; %d decisions within _near's margins" % near)
+    assert rows[0] == 0 and rows[3] == 0
+    for code, (least, _) in REACH_MINIMA.items():
+        assert rows[code] >= least, (code, rows[code], least)
+
+
+@pytest.mark.gpu
+def test_fisheye_stereo_every_rig_matches_oracle(oracle):
+    """One extraction of the three pairs, fisheye_stereo once per rig on that batch, the first rig
+    once more after the others (mvRightToLeftMatch presets and the counters are per call): l2r,
+    r2l, depth and p3d (bits) and n_matches equal the oracle's for every rig and pair."""
+    import orbslam3lib_amd as og
+    eyes = _reach_eyes()
+    be = og.BatchExtractor(1000, 1.2, 8, 20, 7, width=320, height=240, max_images=6)
+    be.upload(np.stack([im for _, L, R in eyes for im in (L, R)]))
+    be.run(np.array([[0, 320]] * 6, np.int32))  # every keypoint in the stereo rows
+    rows = np.zeros(11, np.int64)
+    for name, R12, t12 in REACH_RIGS + REACH_RIGS[:1]:
+        rig = og.KB8Rig.make(CAM_L2, CAM_R2, R12, t12)
+        be.fisheye_stereo(rig)
+        be.synchronize()
+        for p in range(3):
+            what = "rig %s pair %s " % (name, eyes[p][0])
+            g = be.fisheye_result(p)
+            kl, dl, ml = be.result(2 * p)
+            kr, dr, mr = be.result(2 * p + 1)
+            i1, d1, _, _ = be.matches(p)
+            ref_knn = oracle.knn2(dl[ml:], dr[mr:])
+            np.testing.assert_array_equal(i1, ref_knn[0], err_msg=what + "idx1")
+            np.testing.assert_array_equal(d1, ref_knn[1], err_msg=what + "dist1")
+            r = oracle.fisheye_stereo(kl, ml, kr, mr, i1, d1, rig.as_dict(), _sigma2())
+            np.testing.assert_array_equal(g["l2r"], r["l2r"], err_msg=what + "l2r")
+            np.testing.assert_array_equal(g["r2l"], r["r2l"], err_msg=what + "r2l")
+            np.testing.assert_array_equal(g["depth"].view(np.uint32), r["depth"].view(np.uint32),
+                                          err_msg=what + "depth")
+            np.testing.assert_array_equal(g["p3d"].view(np.uint32), r["p3d"].view(np.uint32), err_msg=what + "p3d")
+            assert g["n_matches"] == r["n_matches"], what
+            rows += np.bincount(r["code"], minlength=11)
+    print("fisheye rigs on the device: rows per code 0..10:", rows.tolist())
+    for code, (least, _) in REACH_MINIMA.items():
+        assert rows[code] >= least, (code, rows[code], least)
+    be.close()

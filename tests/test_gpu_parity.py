@@ -154,6 +154,45 @@ def test_knn2_ties_and_edges(oracle):
         ref = oracle.knn2(q, tt)
         for a, b in zip(got, ref):
             np.testing.assert_array_equal(a, b)
+    # the ends of the key range 4096 (256 - 2H) + 4095 - t: random descriptors keep H near 128
+    seen = set()
+    for nq in (33, 257):       # one past a wave, one past a workgroup
+        for nt in (31, 33, 4097):
+            for what, qq, tt in _structured_knn2(nq, nt):
+                got = bf.knnMatch(qq, tt, 2)
+                ref = oracle.knn2(qq, tt)
+                for name, a, b in zip(("idx1", "dist1", "idx2", "dist2"), got, ref):
+                    np.testing.assert_array_equal(a, b, err_msg="nq %d nt %d %s %s" % (nq, nt, what, name))
+                seen.update(zip(ref[1].tolist(), ref[3].tolist()))
+                seen.update(("rows", i, j) for i, j in zip(ref[0].tolist(), ref[2].tolist()))
+    # what the cases are for: H = 256 best and second best, H = 0 twice, winners on both sides of
+    # a 32-row tile boundary and of the 4096-row segment
+    assert {(256, 256), (0, 0), (255, 255), (0, 256), ("rows", 31, 32), ("rows", 4095, 4096)} <= seen
+
+
+def _structured_knn2(nq, nt):
+    """(name, query, train) sets: all-zero, all-ones and one-hot rows; exact complements of the
+    queries at train rows 0, 31, 32, 4095 and 4096; train sets of one repeated row, where only the
+    index breaks the tie, also with the first equal row just before a tile / segment boundary."""
+    onehot = np.zeros((256, 32), np.uint8)
+    onehot[np.arange(256), np.arange(256) // 8] = 1 << (np.arange(256) % 8)
+    rows = np.concatenate([np.zeros((1, 32), np.uint8), np.full((1, 32), 255, np.uint8), onehot])
+    q = rows[:nq]
+    t = np.resize(np.roll(rows, 7, axis=0), (nt, 32)).copy()
+    for r in (0, 31, 32, 4095, 4096):
+        if r < nt:
+            t[r] = ~q[r % nq]
+    yield "complements", q, t
+    t = np.tile(~q[0], (nt, 1))
+    t[0] = q[0]
+    yield "q[0] then ~q[0]", q, t  # H = 0 best and H = 256 second best for the all-zero query
+    for j in (0, 1, 7):
+        yield "all rows ~q[%d]" % j, q, np.tile(~q[j], (nt, 1))
+    for k in (min(31, nt - 2), 4095):
+        if k + 2 <= nt:
+            t = np.tile(q[1], (nt, 1))
+            t[:k] = q[0]
+            yield "first equal row %d" % k, q, t
 
 
 def test_euroc_size_and_other_frames(oracle):

@@ -4,22 +4,30 @@ bit-exact on mvuRight / mvDepth / SAD (GPU tests).
 
 Parity status: unpinned against the reference itself (Frame.cc needs OpenCV + the SLAM stack and
 cannot be built here; the reference ships no fixtures for it) -- the oracle restates the
-function line by line and is cross-checked by the Python restatement below."""
+function line by line and is cross-checked by the Python restatement below, outputs and per-row
+decision codes / flags alike.  tests/stereo_scenes.py holds the pairs that reach every live rule;
+test_scenes_exercise_every_rule counts what they reach."""
+import collections
 import math
 
 import numpy as np
 import pytest
 
 from orbslam3lib_amd import synth
+from tests import stereo_scenes as SC
 
 F32 = np.float32
 
 
 def _py_stereo(kl, dl, kr, dr, pl, pr, mbf, mb, scale, inv_scale):
-    """Independent restatement in numpy float32 scalars (no FMA: one rounding per op)."""
+    """Independent restatement in numpy float32 scalars (no FMA: one rounding per op) ->
+    (mvuRight, mvDepth, sad, code, flags), codes and flags as oracle.stereo_matches_coded."""
     nL = len(kl)
     ur = np.full(nL, -1, np.float32)
     dep = np.full(nL, -1, np.float32)
+    sad = np.full(nL, -1, np.int32)
+    code = np.zeros(nL, np.int32)
+    flags = np.zeros(nL, np.int32)
     nrows = pl[0].shape[0]
     rows = [[] for _ in range(nrows)]
     for iR in range(len(kr)):
@@ -32,49 +40,84 @@ def _py_stereo(kl, dl, kr, dr, pl, pr, mbf, mb, scale, inv_scale):
     pairs = []
     for iL in range(nL):
         uL, vL, oct_ = F32(kl["x"][iL]), F32(kl["y"][iL]), int(kl["octave"][iL])
+        if not 0 <= int(vL) < nrows:
+            code[iL] = 1
+            continue
         cands = rows[int(vL)]
         if not cands:
+            code[iL] = 2
             continue
         minU, maxU = F32(uL - maxD), F32(uL - F32(0))
         if maxU < 0:
+            code[iL] = 3
             continue
-        best, bi = 100, 0
-        for iR in cands:
-            if not (oct_ - 1 <= kr["octave"][iR] <= oct_ + 1):
-                continue
-            if minU <= kr["x"][iR] <= maxU:
-                d = int(np.unpackbits(np.bitwise_xor(dl[iL], dr[iR])).sum())
-                if d < best:
-                    best, bi = d, iR
+        in_range = [iR for iR in cands if minU <= kr["x"][iR] <= maxU]
+        gated = [iR for iR in in_range if oct_ - 1 <= kr["octave"][iR] <= oct_ + 1]
+        if len(gated) < len(in_range):
+            flags[iL] |= 4
+        if not gated:
+            code[iL] = 4
+            continue
+        ham = [int(np.unpackbits(np.bitwise_xor(dl[iL], dr[iR])).sum()) for iR in gated]
+        best = min(ham)
+        bi = gated[ham.index(best)]  # the first (lowest index) of the best
+        if best < 100:
+            if ham.count(best) >= 2:
+                flags[iL] |= 1
+            if kr["octave"][bi] != oct_:
+                flags[iL] |= 8
         if best >= 75:
+            code[iL] = 5
             continue
+        band = int(math.ceil(F32(2.0) * F32(scale[min(oct_ + 1, len(pl) - 1)]))) + 1
+        if abs(int(math.floor(kr["y"][bi])) - int(vL)) == band:
+            flags[iL] |= 64
         sf = F32(inv_scale[oct_])
         rnd = lambda v: F32(math.floor(abs(v) + 0.5) * (1 if v >= 0 else -1))  # std::round
         suL, svL, suR0 = rnd(F32(uL * sf)), rnd(F32(vL * sf)), rnd(F32(F32(kr["x"][bi]) * sf))
-        W = pl[oct_].shape[1]
-        if suR0 < 0 or suR0 + 11 >= W:
+        H, W = pl[oct_].shape
+        if suR0 + 5 - 5 < 0 or suR0 + 5 + 5 + 1 >= W:  # iniu, endu
+            code[iL] = 6
             continue
-        IL = pl[oct_][int(svL) - 5:int(svL) + 6, int(suL) - 5:int(suL) + 6].astype(np.int32)
+        top, left, right = int(svL) - 5, int(suL) - 5, int(suR0) - 10
+        if top < 0 or top + 11 > H or left < 0 or left + 11 > W or right < 0:  # the added guards
+            code[iL] = 7
+            continue
+        IL = pl[oct_][top:top + 11, left:left + 11].astype(np.int32)
         dists = []
         for inc in range(-5, 6):
             c = int(suR0) + inc
-            IR = pr[oct_][int(svL) - 5:int(svL) + 6, c - 5:c + 6].astype(np.int32)
+            IR = pr[oct_][top:top + 11, c - 5:c + 6].astype(np.int32)
             dists.append(F32(np.abs(IL - IR).sum()))
+        if dists.count(min(dists)) >= 2:
+            flags[iL] |= 2
+        if max(dists) >= 16384:
+            flags[iL] |= 16
         bestinc = int(np.argmin(dists)) - 5  # first minimum
         if abs(bestinc) == 5:
+            code[iL] = 8
             continue
         d1, d2, d3 = dists[bestinc + 4], dists[bestinc + 5], dists[bestinc + 6]
         deltaR = F32(F32(d1 - d3) / F32(F32(2.0) * F32(F32(d1 + d3) - F32(F32(2.0) * d2))))
         if deltaR < -1 or deltaR > 1:
+            code[iL] = 9
             continue
         buR = F32(F32(scale[oct_]) * F32(F32(suR0 + F32(bestinc)) + deltaR))
         disp = F32(uL - buR)
-        if disp >= 0 and disp < maxD:
+        if disp < 0:
+            code[iL] = 10
+        elif not disp < maxD:
+            code[iL] = 11
+        else:
+            code[iL] = 12
             if disp <= 0:
                 disp = F32(0.01)
                 buR = F32(float(uL) - 0.01)
+                code[iL] = 13
+                flags[iL] |= 32
             dep[iL] = F32(F32(mbf) / disp)
             ur[iL] = buR
+            sad[iL] = int(d2)
             pairs.append((int(d2), iL))
     if pairs:
         pairs.sort()
@@ -82,7 +125,8 @@ def _py_stereo(kl, dl, kr, dr, pl, pr, mbf, mb, scale, inv_scale):
         for d, i in pairs:
             if not (F32(d) < th):
                 ur[i] = dep[i] = -1
-    return ur, dep
+                code[i] = 14
+    return ur, dep, sad, code, flags
 
 
 def _frame(oracle, seed, shift=12, h=480, w=640, nf=2000):
@@ -94,20 +138,164 @@ def _frame(oracle, seed, shift=12, h=480, w=640, nf=2000):
     return L, R, kl, dl, kr, dr
 
 
+def _same_as_restatement(oracle, kl, dl, kr, dr, pl, pr, mbf, mb, scale_factor=1.2):
+    """Oracle (coded and plain entry points) == _py_stereo on every output, code and flag."""
+    o = oracle.stereo_matches_coded(kl, dl, kr, dr, pl, pr, mbf, mb, scale_factor)
+    plain = oracle.stereo_matches(kl, dl, kr, dr, pl, pr, mbf, mb, scale_factor)
+    for a, b in zip(plain, o[:3]):  # the codes change nothing
+        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+    scale, inv_scale, _, _ = oracle.scale_factors(scale_factor, len(pl))
+    py = _py_stereo(kl, dl, kr, dr, pl, pr, mbf, mb, scale, inv_scale)
+    for what, a, b in zip(("uRight", "depth", "sad", "code", "flags"), o, py):
+        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32), err_msg=what)
+    return o
+
+
 def test_oracle_matches_python_restatement(oracle):
     L, R, kl, dl, kr, dr = _frame(oracle, 2)
     pl, pr = oracle.pyramid(L), oracle.pyramid(R)
     mbf, mb = 47.9, float(np.float32(47.9) / np.float32(435.2))
-    ur, dep, sad = oracle.stereo_matches(kl, dl, kr, dr, pl, pr, mbf, mb)
-    scale, inv_scale, _, _ = oracle.scale_factors()
-    pur, pdep = _py_stereo(kl, dl, kr, dr, pl, pr, mbf, mb, scale, inv_scale)
-    np.testing.assert_array_equal(ur, pur)
-    np.testing.assert_array_equal(dep, pdep)
+    ur, dep, sad, code, flags = _same_as_restatement(oracle, kl, dl, kr, dr, pl, pr, mbf, mb)
     assert (ur >= 0).sum() > len(kl) // 3  # the 12 px disparity is found for most keypoints
     ok = ur >= 0
     assert np.abs((kl["x"][ok] - ur[ok]) - 12).max() < 1.0
+    np.testing.assert_array_equal(ok, (code == 12) | (code == 13))
+    np.testing.assert_array_equal(sad >= 0, code >= 12)
 
 
+# ---------------------------------------------------------------------------------------------
+# The scenes of tests/stereo_scenes.py on the CPU: what they reach, and the restatement on them
+_CODED = {}
+
+
+def _coded(oracle, name):
+    """Extraction, pyramids and the coded oracle of one scene, computed once per session."""
+    if name not in _CODED:
+        s = SC.by_name(name)
+        kw = dict(nfeatures=s.nfeatures, scale_factor=s.scale_factor, nlevels=s.nlevels)
+        kl, dl, _ = oracle.extract(s.left, **kw)
+        kr, dr, _ = oracle.extract(s.right, **kw)
+        pl = oracle.pyramid(s.left, s.scale_factor, s.nlevels)
+        pr = oracle.pyramid(s.right, s.scale_factor, s.nlevels)
+        out = oracle.stereo_matches_coded(kl, dl, kr, dr, pl, pr, s.mbf, s.mb, s.scale_factor)
+        _CODED[name] = dict(zip(("uRight", "depth", "sad", "code", "flags"), out), kl=kl, dl=dl, kr=kr, dr=dr,
+                            pl=pl, pr=pr)
+    return _CODED[name]
+
+
+def test_scenes_exercise_every_rule(oracle):
+    """The scenes reach what they are named for: rows per decision code and flag of the coded
+    oracle, summed over the scene set, against the minima of stereo_scenes.MINIMA."""
+    rows = collections.Counter()
+    sparse_counts = []
+    median_sensitive = set()  # parities of the sparse counts where k - 1, k and k + 1 keep different rows
+    SC.check_contexts()
+    for s in SC.scenes():
+        c = _coded(oracle, s.name)
+        code, flags, nL = c["code"], c["flags"], len(c["kl"])
+        for k in range(1, 15):
+            rows["code%d" % k] += int((code == k).sum())
+        if nL == 0:
+            rows["no_left_rows"] += 1
+        rows["row_list_missing"] += int(((code == 1) | (code == 2)).sum())
+        if (code == 14).sum() >= 10 and (code == 12).sum() >= 10:
+            rows["pairs_with_kept_and_median_rejected"] += 1
+        rows["hamming_tie_then_sad"] += int((((flags & oracle.STF_HAMMING_TIE) != 0) & (code >= 6)).sum())
+        for f, nm in ((oracle.STF_SAD_TIE, "sad_tie"), (oracle.STF_OCTAVE_GATE, "octave_gate"),
+                      (oracle.STF_NEIGHBOUR_OCTAVE, "neighbour_octave"), (oracle.STF_SAD_HIGH, "sad_high"),
+                      (oracle.STF_BAND_EDGE, "band_edge")):
+            rows[nm] += int(((flags & f) != 0).sum())
+        rows["accepted_sad_high"] += int((c["sad"] >= 16384).sum())
+        # code 13 = went through disparity <= 0 AND kept by the median rule
+        assert ((code == 13) <= ((flags & oracle.STF_ZERO_BRANCH) != 0)).all()
+        np.testing.assert_array_equal(c["uRight"] >= 0, (code == 12) | (code == 13))
+        if s.name.startswith("sparse_"):
+            sparse_counts.append(int((c["sad"] >= 0).sum()))
+            # would another median index show?  rows kept with k = count / 2 - 1, k, k + 1
+            acc = np.sort(c["sad"][c["sad"] >= 0]).astype(np.float32)
+            kept = [int((acc < F32(F32(1.5) * F32(1.4)) * acc[k]).sum()) for k in
+                    (len(acc) // 2 - 1, len(acc) // 2, len(acc) // 2 + 1)]
+            assert kept[1] == ((code == 12) | (code == 13)).sum()
+            if len(set(kept)) == 3:
+                median_sensitive.add(len(acc) % 2)
+        # Dead guards.  The extractor keeps keypoints at least 19 px (EDGE_THRESHOLD) inside their
+        # own level.  The left keypoint is scaled to its own level: uL >= 0 (code 3) and its
+        # 11 x 11 window is inside (code 7, r0 / c0).  The best right keypoint comes from that
+        # level or a neighbour; from the finer one its margin shrinks to 19 / 1.2 = 15.8 px at the
+        # left keypoint's level, still more than the 10 px (cr) and 11 px (endu) the 11 shifts
+        # need (codes 6, 7).  At scale factor 2.0 that margin is 9.5 px, so this is asserted for
+        # the 1.2 scenes only.  Code 9 is dead at any scale: bestincR is the FIRST minimum and not
+        # at an end, so d1 > d2 and d3 >= d2, hence |d1 - d3| <= (d1 - d2) + (d3 - d2) =
+        # d1 + d3 - 2 d2 > 0 and |deltaR| <= 0.5 (integers below 2^15: exact in float).
+        assert (code == 9).sum() == 0, s.name
+        if s.scale_factor == 1.2:
+            for k in (3, 6, 7, 9):
+                assert (code == k).sum() == 0, (s.name, k)
+    print("stereo scenes reach:", dict(rows), "sparse accepted:", sparse_counts)
+    for key, least in SC.MINIMA.items():
+        assert rows[key] >= least, (key, rows[key], least)
+    assert all(0 < n <= 25 for n in sparse_counts), sparse_counts
+    assert {n % 2 for n in sparse_counts} == {0, 1}, sparse_counts
+    assert median_sensitive == {0, 1}
+
+
+@pytest.mark.parametrize("name", SC.NAMES)
+def test_restatement_on_scenes(oracle, name):
+    """Outputs, codes and flags of the oracle against _py_stereo on every scene: the ties, the
+    zero-disparity branch, small counts, another scale factor, odd level sizes."""
+    s, c = SC.by_name(name), _coded(oracle, name)
+    o = _same_as_restatement(oracle, c["kl"], c["dl"], c["kr"], c["dr"], c["pl"], c["pr"], s.mbf, s.mb,
+                             s.scale_factor)
+    np.testing.assert_array_equal(o[3], c["code"])
+
+
+def test_window_guards_on_hand_made_keypoints(oracle):
+    """Codes 6 (iniu / endu) and 7 (the added window guards) on hand-made keypoint arrays over a
+    real pyramid: left / right keypoints with equal descriptors on one row, placed so that the
+    11-shift window leaves the level on each side.  The extractor never produces such keypoints
+    (see test_scenes_exercise_every_rule), so only the oracle and the restatement can be fed them:
+    this proves that the two state the same guard, not that the kernel has it."""
+    L, R = synth.stereo_pair(240, 320, 0)
+    pl, pr = oracle.pyramid(L), oracle.pyramid(R)
+    rng = np.random.default_rng(3)
+    # (uL, vL, uR, octave, expected code): level 0 is 320 x 240, level 2 is 222 x 167
+    W2 = pl[2].shape[1]
+    s2 = float(oracle.scale_factors()[0][2])
+    cases = [
+        (300.0, 100.0, 0.4, 0, 7),      # scaleduR0 = 0: iniu = 0 passes, cr = -10
+        (300.0, 101.0, 9.4, 0, 7),      # cr = -1
+        (300.0, 102.0, 10.0, 0, None),  # cr = 0: the SAD runs
+        (315.0, 103.0, 309.0, 0, 6),    # endu = 320 >= cols
+        (315.0, 104.0, 308.0, 0, 7),    # endu = 319 passes, c0 + 11 = 321 > cols
+        (314.0, 105.0, 308.0, 0, None),  # c0 + 11 = 320: inside
+        (100.0, 4.0, 90.0, 0, 7),       # r0 = -1
+        (100.0, 5.0, 90.0, 0, None),
+        (100.0, 235.0, 90.0, 0, 7),     # r0 + 11 = 241 > rows
+        (100.0, 234.0, 90.0, 0, None),
+        (50.0, 106.0, -0.6, 0, 6),      # iniu = -1 (maxD is wider than the frame)
+        ((W2 - 3) * s2, 120.0, (W2 - 11) * s2, 2, 6),   # endu = cols at level 2
+        ((W2 - 3) * s2, 124.0, (W2 - 12) * s2, 2, 7),   # c0 + 11 > cols at level 2
+        (150.0 * s2, 128.0, 9.0 * s2, 2, 7),            # cr = -1 at level 2
+    ]
+    n = len(cases)
+    kl, kr = np.zeros(n, oracle.KP_DTYPE), np.zeros(n, oracle.KP_DTYPE)
+    for i, (uL, vL, uR, octv, _) in enumerate(cases):
+        kl["x"][i], kl["y"][i], kl["octave"][i] = uL, vL, octv
+        kr["x"][i], kr["y"][i], kr["octave"][i] = uR, vL, octv
+    dl = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    dr = dl.copy()  # Hamming 0 with the own partner, ~128 with the others
+    ur, dep, sad, code, flags = _same_as_restatement(oracle, kl, dl, kr, dr, pl, pr, SC.MBF, SC.MB)
+    for i, (_, _, _, _, want) in enumerate(cases):
+        if want is None:
+            assert code[i] >= 8, (i, code[i])
+        else:
+            assert code[i] == want, (i, code[i], want)
+            assert ur[i] == -1 and dep[i] == -1 and sad[i] == -1
+
+
+
+# ---------------------------------------------------------------------------------------------
+# GPU: the gfx950 kernels against the oracle
 def _gpu_vs_oracle(oracle, imgs_pairs, mbf, mb, w=640, h=480, L=8, nf=2000):
     import orbslam3lib_amd as og
     n = 2 * len(imgs_pairs)
@@ -131,8 +319,14 @@ def _gpu_vs_oracle(oracle, imgs_pairs, mbf, mb, w=640, h=480, L=8, nf=2000):
 def test_gpu_stereo_matches_bit_exact(oracle):
     pairs = [synth.stereo_pair(480, 640, s) for s in range(4)]
     L0 = pairs[0][0]
-    pairs.append((L0, L0.copy()))                 # zero disparity: the disparity <= 0 branch
-    pairs.append((L0, np.roll(L0, -3, axis=1)))   # 3 px disparity
+    # identical eyes: every SAD is 0, so the median is 0, thDist is 0 and the median rule rejects
+    # every accepted row (0 < 0 fails): this pair checks sad and the median rule with a zero
+    # median; uRight / depth are -1 on every row (the disparity <= 0 branch's VALUES are checked
+    # by test_gpu_stereo_zero_disparity_is_visible)
+    pairs.append((L0, L0.copy()))
+    # 3 px disparity, noise-free: SAD is 0 nearly everywhere, so this pair too checks sad and the
+    # median rule near a zero median, and few depths
+    pairs.append((L0, np.roll(L0, -3, axis=1)))
     pairs.append((L0, np.zeros_like(L0)))         # empty right image: no candidates at all
     pairs.append((synth.frame(480, 640, 9), synth.frame(480, 640, 10)))  # unrelated views
     _gpu_vs_oracle(oracle, pairs, 47.9, float(np.float32(47.9) / np.float32(435.2)))
@@ -149,3 +343,101 @@ def test_gpu_stereo_matches_narrow_disparity_range(oracle):
 def test_gpu_stereo_matches_euroc_and_1080p(oracle):
     _gpu_vs_oracle(oracle, [synth.stereo_pair(480, 752, 7)], 47.9, 0.11, w=752, h=480)
     _gpu_vs_oracle(oracle, [synth.stereo_pair(1080, 1920, 8)], 47.9, 0.11, w=1920, h=1080, L=12, nf=5000)
+
+
+def _same_rows(got, want, code, what):
+    """Bit equality; a mismatch names the first row and the oracle's decision code there."""
+    g, w = got.view(np.uint32), want.view(np.uint32)
+    assert len(g) == len(w), "%s: %d rows, the oracle has %d" % (what, len(g), len(w))
+    bad = np.flatnonzero(g != w)
+    assert len(bad) == 0, "%s: %d rows differ, first row %d (oracle code %d): %r != %r" % (
+        what, len(bad), bad[0], code[bad[0]], got[bad[0]], want[bad[0]])
+
+
+def _context(names):
+    import orbslam3lib_amd as og
+    s = SC.by_name(names[0])
+    h, w = s.left.shape
+    return og.BatchExtractor(s.nfeatures, s.scale_factor, s.nlevels, 20, 7, width=w, height=h,
+                             max_images=2 * len(names))
+
+
+def _run_scenes(oracle, be, names, tag=""):
+    """One upload + extraction of the named scenes (pair p = names[p]), stereo_matches once per
+    (mbf, mb) among them, each scene against the coded oracle on the device's own keypoints.
+    Returns {name: (device results, oracle results, left keypoints)}."""
+    sc = [SC.by_name(n) for n in names]
+    be.upload(np.stack([im for s in sc for im in (s.left, s.right)]))
+    be.run()
+    out = {}
+    for mbf, mb in sorted({(s.mbf, s.mb) for s in sc}):
+        be.stereo_matches(mbf, mb)
+        be.synchronize()
+        for p, s in enumerate(sc):
+            if (s.mbf, s.mb) != (mbf, mb):
+                continue
+            kl, dl, _ = be.result(2 * p)
+            kr, dr, _ = be.result(2 * p + 1)
+            ref = oracle.stereo_matches_coded(kl, dl, kr, dr, oracle.pyramid(s.left, s.scale_factor, s.nlevels),
+                                              oracle.pyramid(s.right, s.scale_factor, s.nlevels), mbf, mb,
+                                              s.scale_factor)
+            got = be.stereo_result(p)
+            for k, what in ((2, "sad"), (0, "uRight"), (1, "depth")):
+                _same_rows(got[k], ref[k], ref[3], "%sscene %s pair %d %s" % (tag, s.name, p, what))
+            out[s.name] = (got, ref, kl)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", list(SC.CONTEXTS))
+def test_gpu_stereo_scenes(oracle, key):
+    """Every scene of tests/stereo_scenes.py, one context and one extraction per frame shape /
+    parameter set: uRight, depth (bits) and sad equal the oracle's."""
+    names = list(SC.CONTEXTS[key])
+    be = _context(names)
+    res = _run_scenes(oracle, be, names)
+    codes = np.concatenate([r[1][3] for r in res.values()])
+    print("stereo scenes %s: codes %s" % (names, np.bincount(codes, minlength=15).tolist()))
+    be.close()
+
+
+@pytest.mark.gpu
+def test_gpu_stereo_zero_disparity_is_visible(oracle):
+    """The disparity <= 0 branch with its results kept by the median rule: on those rows uRight is
+    float(double(uL) - 0.01) and depth is mbf / 0.01f, computed here, and both equal the oracle."""
+    be = _context(["zero_visible"])
+    (gur, gdep, _), (ur, dep, _, code, flags), kl = _run_scenes(oracle, be, ["zero_visible"])["zero_visible"]
+    rows = np.flatnonzero(code == oracle.ST_ACCEPTED_ZERO)
+    print("zero_visible: %d rows through disparity <= 0 and kept" % len(rows))
+    assert len(rows) >= 5
+    uL = kl["x"][rows]
+    want_ur = (uL.astype(np.float64) - 0.01).astype(np.float32)
+    want_dep = np.full(len(rows), F32(SC.MBF) / F32(0.01), np.float32)
+    # (A float subtraction uL - 0.01f cannot be told from the double one here or anywhere else: the
+    # two round to the same float for every coordinate n * scale[level] the extractor can produce
+    # up to 1920 px at scale factors 1.2 and 2.0.  A changed constant, a lost -1 reset or a
+    # different depth constant does show.)
+    for got, ref, want, what in ((gur, ur, want_ur, "uRight"), (gdep, dep, want_dep, "depth")):
+        np.testing.assert_array_equal(got[rows].view(np.uint32), ref[rows].view(np.uint32), err_msg=what)
+        np.testing.assert_array_equal(got[rows].view(np.uint32), want.view(np.uint32), err_msg=what)
+    assert (gur[rows] >= 0).all()
+    be.close()
+
+
+@pytest.mark.gpu
+def test_gpu_stereo_context_reuse(oracle):
+    """One context, three runs: a dense batch, then fewer pairs in another order with an empty
+    left and an empty right eye, then the dense batch again.  Row tables, scatter cursors and the
+    -1 resets must not survive from the larger run: every run equals the oracle."""
+    a = ["natural12", "period6b", "zero_visible", "vshift5", "period4"]
+    b = ["blank_left", "vshift5", "blank_right", "narrow8"]
+    be = _context(a)
+    first = _run_scenes(oracle, be, a, "run A ")
+    mid = _run_scenes(oracle, be, b, "run B ")
+    assert len(mid["blank_left"][0][0]) == 0
+    assert len(mid["blank_right"][0][0]) > 0 and (mid["blank_right"][0][0] == -1).all()
+    again = _run_scenes(oracle, be, a, "run A again ")
+    for n in a:
+        for x, y in zip(first[n][0], again[n][0]):
+            np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
+    be.close()
