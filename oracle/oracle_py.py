@@ -361,9 +361,26 @@ MP_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), (
                      ("proj_yr", "<f4"), ("view_cos_r", "<f4"), ("level_r", "<i4")])
 
 
-def search_by_projection(mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block=None,
-                         th=1.0, nnratio=0.8, far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
-    """ORBmatcher::SearchByProjection (ORBmatcher.cc:44-214), pinhole -> (match [n], nmatches)."""
+SBP_RECORD_DTYPE = np.dtype([("code", "<i4"), ("flags", "<i4"), ("ncand", "<i4"), ("rank_best", "<i4"),
+                             ("rank_second", "<i4"), ("assigned", "<i4", (2,))])
+# decision codes / flags of the coded projection searches (ORACLE_SBP_* in orb_oracle.h)
+(SBP_NO_WINDOW, SBP_NOT_IN_VIEW, SBP_FAR, SBP_BAD, SBP_LEVEL_RANGE, SBP_LEVEL_R_M1, SBP_EXIT_MINX, SBP_EXIT_MAXX,
+ SBP_EXIT_MINY, SBP_EXIT_MAXY, SBP_NO_KEYPOINT, SBP_ALL_TAKEN, SBP_TH_HIGH, SBP_RATIO, SBP_ACCEPT_LEVELS,
+ SBP_ACCEPT_RATIO, SBP_SKIPPED) = range(17)
+SBP_CODE_NAMES = ("no_window", "not_in_view", "far", "bad", "level_range", "level_r_m1", "exit_minx", "exit_maxx",
+                  "exit_miny", "exit_maxy", "no_keypoint", "all_taken", "th_high", "ratio", "accept_levels",
+                  "accept_ratio", "skipped")
+SBP_FLAG_NAMES = ("tie_best", "best_eq_second", "bd_100", "ratio_eq", "edge", "uright_reject", "uright_eq", "far_eq",
+                  "clipped", "cell_int", "taken_skip", "overwrote", "partner", "freed_incall", "freed_precall",
+                  "own_partner", "double_assign", "skipped_right", "tie_second")
+(SBPF_TIE_BEST, SBPF_BEST_EQ_SECOND, SBPF_BD_100, SBPF_RATIO_EQ, SBPF_EDGE, SBPF_URIGHT_REJECT, SBPF_URIGHT_EQ,
+ SBPF_FAR_EQ, SBPF_CLIPPED, SBPF_CELL_INT, SBPF_TAKEN_SKIP, SBPF_OVERWROTE, SBPF_PARTNER, SBPF_FREED_INCALL,
+ SBPF_FREED_PRECALL, SBPF_OWN_PARTNER, SBPF_DOUBLE_ASSIGN, SBPF_SKIPPED_RIGHT,
+ SBPF_TIE_SECOND) = (1 << b for b in range(19))
+
+
+def _sbp_call(coded, mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block, th, nnratio,
+              far_points, th_far, scale_factor, nlevels):
     mps = np.ascontiguousarray(mps, dtype=MP_DTYPE)
     n = len(octave)
     xy = np.ascontiguousarray(xy_un, dtype=np.float32).reshape(-1, 2)
@@ -378,18 +395,36 @@ def search_by_projection(mps, xy_un, octave, desc, uright, bounds, cell_start, c
     blk = None if kp_block is None else np.ascontiguousarray(kp_block, dtype=np.uint8)
     scale = scale_factors(scale_factor, nlevels)[0]
     match = np.zeros(max(n, 1), np.int32)
-    nm = lib().oracle_search_by_projection(
-        _p(mps) if len(mps) else None, len(mps), _p(xy) if n else None, _p(octv) if n else None,
-        _p(d) if n else None, _p(ur) if ur is not None else None, n, _p(b), _p(cs), _p(ci), _p(scale), nlevels,
-        _p(blk) if blk is not None else None, C.c_float(th), C.c_float(nnratio), int(far_points),
-        C.c_float(th_far), _p(match))
-    return match[:n], nm
+    args = [_p(mps) if len(mps) else None, len(mps), _p(xy) if n else None, _p(octv) if n else None,
+            _p(d) if n else None, _p(ur) if ur is not None else None, n, _p(b), _p(cs), _p(ci), _p(scale), nlevels,
+            _p(blk) if blk is not None else None, C.c_float(th), C.c_float(nnratio), int(far_points),
+            C.c_float(th_far), _p(match)]
+    if not coded:
+        return match[:n], lib().oracle_search_by_projection(*args)
+    recs = np.zeros((max(len(mps), 1), 2), SBP_RECORD_DTYPE)
+    nm = lib().oracle_search_by_projection_coded(*args, _p(recs))
+    return match[:n], nm, recs[:len(mps)]
 
 
-def search_by_projection2(mps, left, right, bounds, l2r=None, r2l=None, kp_block=None, th=1.0, nnratio=0.8,
-                          far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
-    """Two-camera SearchByProjection (Nleft != -1).  left / right = (xy [n,2], octave [n],
-    desc [n,32], cell_start, cell_idx) -> (match [nl + nr], nmatches)."""
+def search_by_projection(mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block=None,
+                         th=1.0, nnratio=0.8, far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
+    """ORBmatcher::SearchByProjection (ORBmatcher.cc:44-214), pinhole -> (match [n], nmatches)."""
+    return _sbp_call(False, mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block, th, nnratio,
+                     far_points, th_far, scale_factor, nlevels)
+
+
+def search_by_projection_coded(mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block=None,
+                               th=1.0, nnratio=0.8, far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
+    """search_by_projection() plus one SBP_RECORD_DTYPE record per map point and window ([nmp, 2];
+    column 1, the right window, stays SBP_NO_WINDOW on a pinhole frame): the first rule that stopped
+    the window (code, SBP_*), what it met (flags, SBPF_*), and the replay data (ncand, rank_best,
+    rank_second, assigned; see orb_oracle.h) -> (match, nmatches, records)."""
+    return _sbp_call(True, mps, xy_un, octave, desc, uright, bounds, cell_start, cell_idx, kp_block, th, nnratio,
+                     far_points, th_far, scale_factor, nlevels)
+
+
+def _sbp2_call(coded, mps, left, right, bounds, l2r, r2l, kp_block, th, nnratio, far_points, th_far, scale_factor,
+               nlevels):
     mps = np.ascontiguousarray(mps, dtype=MP_DTYPE)
 
     def prep(side):
@@ -407,9 +442,28 @@ def search_by_projection2(mps, left, right, bounds, l2r=None, r2l=None, kp_block
     scale = scale_factors(scale_factor, nlevels)[0]
     match = np.zeros(max(nl + nr, 1), np.int32)
     pp = lambda a: _p(a) if a is not None and a.size else None
-    nm = lib().oracle_search_by_projection2(
-        pp(mps), len(mps), pp(L[0]), pp(L[1]), pp(L[2]), nl, _p(L[3]), _p(L[4]),
-        pp(R[0]), pp(R[1]), pp(R[2]), nr, _p(R[3]), _p(R[4]), _p(np.ascontiguousarray(bounds, np.float32)),
-        pp(l2r), pp(r2l), _p(scale), nlevels, pp(blk), C.c_float(th), C.c_float(nnratio), int(far_points),
-        C.c_float(th_far), _p(match))
-    return match[:nl + nr], nm
+    args = [pp(mps), len(mps), pp(L[0]), pp(L[1]), pp(L[2]), nl, _p(L[3]), _p(L[4]),
+            pp(R[0]), pp(R[1]), pp(R[2]), nr, _p(R[3]), _p(R[4]), _p(np.ascontiguousarray(bounds, np.float32)),
+            pp(l2r), pp(r2l), _p(scale), nlevels, pp(blk), C.c_float(th), C.c_float(nnratio), int(far_points),
+            C.c_float(th_far), _p(match)]
+    if not coded:
+        return match[:nl + nr], lib().oracle_search_by_projection2(*args)
+    recs = np.zeros((max(len(mps), 1), 2), SBP_RECORD_DTYPE)
+    nm = lib().oracle_search_by_projection2_coded(*args, _p(recs))
+    return match[:nl + nr], nm, recs[:len(mps)]
+
+
+def search_by_projection2(mps, left, right, bounds, l2r=None, r2l=None, kp_block=None, th=1.0, nnratio=0.8,
+                          far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
+    """Two-camera SearchByProjection (Nleft != -1).  left / right = (xy [n,2], octave [n],
+    desc [n,32], cell_start, cell_idx) -> (match [nl + nr], nmatches)."""
+    return _sbp2_call(False, mps, left, right, bounds, l2r, r2l, kp_block, th, nnratio, far_points, th_far,
+                      scale_factor, nlevels)
+
+
+def search_by_projection2_coded(mps, left, right, bounds, l2r=None, r2l=None, kp_block=None, th=1.0, nnratio=0.8,
+                                far_points=False, th_far=50.0, scale_factor=1.2, nlevels=8):
+    """search_by_projection2() plus the records of search_by_projection_coded(), column 0 for the
+    left window and column 1 for the right one -> (match, nmatches, records)."""
+    return _sbp2_call(True, mps, left, right, bounds, l2r, r2l, kp_block, th, nnratio, far_points, th_far,
+                      scale_factor, nlevels)

@@ -1300,24 +1300,53 @@ void oracle_pack_soa(const oracle_kp* kps, int n, int32_t* x, int32_t* y, int32_
     }
 }
 
-// ---- ORBmatcher::SearchByProjection (ORBmatcher.cc:44-214), pinhole frame ---------------------
+// ---- ORBmatcher::SearchByProjection (ORBmatcher.cc:44-214) ------------------------------------
+// One implementation behind the plain and the coded entry points: rec == nullptr computes the
+// matches alone, and every statement that touches rec only reads the search's state.
 namespace {
+
+struct AreaInfo {
+    int exit = 0;   // which of GetFeaturesInArea's four early returns was taken (1..4), 0: none
+    int flags = 0;  // ORACLE_SBP_F_CLIPPED / _CELL_INT / _EDGE
+};
 
 // Frame::GetFeaturesInArea (Frame.cc:673-735) on the CSR grid.
 void features_in_area(const float* xy_un, const int32_t* octave, const float bounds[4], const int32_t* cs,
                       const int32_t* ci, float x, float y, float r, int minLevel, int maxLevel,
-                      std::vector<int>& out) {
+                      std::vector<int>& out, AreaInfo* info = nullptr) {
     out.clear();
     const float wInv = static_cast<float>(64) / (bounds[1] - bounds[0]);
     const float hInv = static_cast<float>(48) / (bounds[3] - bounds[2]);
-    const int nMinCellX = std::max(0, (int)std::floor((x - bounds[0] - r) * wInv));
-    if (nMinCellX >= 64) return;
-    const int nMaxCellX = std::min(63, (int)std::ceil((x - bounds[0] + r) * wInv));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = std::max(0, (int)std::floor((y - bounds[2] - r) * hInv));
-    if (nMinCellY >= 48) return;
-    const int nMaxCellY = std::min(47, (int)std::ceil((y - bounds[2] + r) * hInv));
-    if (nMaxCellY < 0) return;
+    const float pMinX = (x - bounds[0] - r) * wInv;
+    const int nMinCellX = std::max(0, (int)std::floor(pMinX));
+    if (nMinCellX >= 64) {
+        if (info) info->exit = 1;
+        return;
+    }
+    const float pMaxX = (x - bounds[0] + r) * wInv;
+    const int nMaxCellX = std::min(63, (int)std::ceil(pMaxX));
+    if (nMaxCellX < 0) {
+        if (info) info->exit = 2;
+        return;
+    }
+    const float pMinY = (y - bounds[2] - r) * hInv;
+    const int nMinCellY = std::max(0, (int)std::floor(pMinY));
+    if (nMinCellY >= 48) {
+        if (info) info->exit = 3;
+        return;
+    }
+    const float pMaxY = (y - bounds[2] + r) * hInv;
+    const int nMaxCellY = std::min(47, (int)std::ceil(pMaxY));
+    if (nMaxCellY < 0) {
+        if (info) info->exit = 4;
+        return;
+    }
+    if (info) {
+        if (std::floor(pMinX) < 0 || std::ceil(pMaxX) > 63 || std::floor(pMinY) < 0 || std::ceil(pMaxY) > 47)
+            info->flags |= ORACLE_SBP_F_CLIPPED;
+        for (float p : {pMinX, pMaxX, pMinY, pMaxY})
+            if (p == std::floor(p)) info->flags |= ORACLE_SBP_F_CELL_INT;
+    }
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
         for (int iy = nMinCellY; iy <= nMaxCellY; iy++)
@@ -1328,64 +1357,257 @@ void features_in_area(const float* xy_un, const int32_t* octave, const float bou
                     if (maxLevel >= 0 && octave[k] > maxLevel) continue;
                 }
                 const float distx = xy_un[2 * k] - x, disty = xy_un[2 * k + 1] - y;
+                if (info && (std::fabs(distx) == r || std::fabs(disty) == r)) info->flags |= ORACLE_SBP_F_EDGE;
                 if (std::fabs(distx) < r && std::fabs(disty) < r) out.push_back(k);
             }
 }
 
+// One image of the frame: keypoint k is entry base + k of blocked / match.
+struct SbpSide {
+    const float* xy;
+    const int32_t* oct;
+    const uint8_t* desc;
+    const int32_t* cs;
+    const int32_t* ci;
+    const float* uRight;  // mvuRight (pinhole frames), or nullptr
+    int base;
+};
+
+// The search's state: the occupancy (mvpMapPoints[k] set with Observations() > 0), the occupancy
+// before the call, the assigned map point per keypoint.
+struct SbpState {
+    std::vector<uint8_t> blocked;
+    const uint8_t* blk0;
+    int32_t* match;
+    std::vector<int> cand;
+    std::vector<std::pair<int, int>> pre, live;  // (distance, keypoint) lists of the coded form
+};
+
+enum { SBP_NONE, SBP_RATIO, SBP_ACCEPT };
+
+// One window (:63-139 / :141-207) up to its decision; *best: the accepted keypoint.
+int sbp_window(const SbpSide& S, const float bounds[4], const oracle_map_point& mp, float x, float y, float rs,
+               int lvl, bool right, float nnratio, SbpState& st, oracle_sbp_record* rec, int* best) {
+    AreaInfo info;
+    features_in_area(S.xy, S.oct, bounds, S.cs, S.ci, x, y, rs, lvl - 1, lvl, st.cand, rec ? &info : nullptr);
+    if (rec) rec->flags |= info.flags;
+    if (st.cand.empty()) {
+        if (rec) rec->code = info.exit ? ORACLE_SBP_EXIT_MINX + info.exit - 1 : ORACLE_SBP_NO_KEYPOINT;
+        return SBP_NONE;
+    }
+    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1, bestIdx2 = -1;
+    st.pre.clear();
+    st.live.clear();
+    for (int idx : st.cand) {
+        const int kb = S.base + idx;
+        const bool taken = st.blocked[kb] != 0;
+        const bool pre = rec && !(st.blk0 && st.blk0[kb]);  // a candidate under the pre-call occupancy
+        if (rec && taken && st.match[kb] != -1) rec->flags |= ORACLE_SBP_F_TAKEN_SKIP;
+        if (taken && !pre) continue;
+        if (S.uRight && S.uRight[idx] > 0) {
+            const float er = std::fabs(mp.proj_xr - S.uRight[idx]);
+            if (rec && er == rs) rec->flags |= ORACLE_SBP_F_URIGHT_EQ;
+            if (er > rs) {
+                if (rec) rec->flags |= ORACLE_SBP_F_URIGHT_REJECT;
+                continue;
+            }
+        }
+        const int dist = oracle_descriptor_distance(mp.desc, S.desc + (size_t)idx * 32);
+        if (pre) st.pre.emplace_back(dist, idx);
+        if (taken) continue;
+        if (rec) st.live.emplace_back(dist, idx);
+        if (dist < bestDist) {
+            bestDist2 = bestDist;
+            bestDist = dist;
+            bestLevel2 = bestLevel;
+            bestLevel = S.oct[idx];
+            bestIdx2 = bestIdx;
+            bestIdx = idx;
+        } else if (dist < bestDist2) {
+            bestLevel2 = S.oct[idx];
+            bestDist2 = dist;
+            bestIdx2 = idx;
+        }
+    }
+    if (rec) {
+        // ranks in the (distance, window position) order of the pre-call candidates
+        std::stable_sort(st.pre.begin(), st.pre.end(),
+                         [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+        const int n = (int)st.pre.size();
+        rec->ncand = rec->rank_best = rec->rank_second = n;
+        for (int j = 0; j < n; ++j) {
+            if (st.pre[j].second == bestIdx) rec->rank_best = j;
+            if (st.pre[j].second == bestIdx2) rec->rank_second = j;
+        }
+        int nb = 0, ns = 0;
+        for (const auto& c : st.live) nb += c.first == bestDist, ns += c.first == bestDist2;
+        if (nb > 1) rec->flags |= ORACLE_SBP_F_TIE_BEST;
+        if (bestDist2 < 256 && bestDist2 > bestDist && ns > 1) rec->flags |= ORACLE_SBP_F_TIE_SECOND;
+        if (bestDist < 256 && bestDist == bestDist2) rec->flags |= ORACLE_SBP_F_BEST_EQ_SECOND;
+        if (bestDist == 100) rec->flags |= ORACLE_SBP_F_BD_100;
+    }
+    if (bestDist > 100) {  // TH_HIGH
+        if (rec) rec->code = bestIdx < 0 ? ORACLE_SBP_ALL_TAKEN : ORACLE_SBP_TH_HIGH;
+        return SBP_NONE;
+    }
+    if (rec && bestLevel == bestLevel2 && bestDist == nnratio * bestDist2) rec->flags |= ORACLE_SBP_F_RATIO_EQ;
+    if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) {
+        if (rec) rec->code = ORACLE_SBP_RATIO;
+        return SBP_RATIO;
+    }
+    // :132 asks again on the left (never false, short of a NaN ratio); the right window does not
+    if (!right && !(bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2)) return SBP_NONE;
+    if (rec) rec->code = bestLevel != bestLevel2 ? ORACLE_SBP_ACCEPT_LEVELS : ORACLE_SBP_ACCEPT_RATIO;
+    *best = bestIdx;
+    return SBP_ACCEPT;
+}
+
+// F.mvpMapPoints[k] = pMP, with what it does to the occupancy.
+void sbp_assign(SbpState& st, int k, int i, const oracle_map_point& mp, oracle_sbp_record* rec, int slot) {
+    const bool obs = (mp.flags & ORACLE_MP_HAS_OBS) != 0;
+    if (rec) {
+        if (st.match[k] != -1) rec->flags |= ORACLE_SBP_F_OVERWROTE;
+        if (!obs && st.blocked[k])
+            rec->flags |= st.match[k] != -1 ? ORACLE_SBP_F_FREED_INCALL : ORACLE_SBP_F_FREED_PRECALL;
+        rec->assigned[slot] = k;
+    }
+    st.match[k] = i;
+    st.blocked[k] = obs ? 1 : 0;
+}
+
+int sbp_search(const oracle_map_point* mps, int nmp, const SbpSide& L, const SbpSide* R, int n,
+               const float bounds[4], const int32_t* l2r, const int32_t* r2l, const float* scale, int nlevels,
+               const uint8_t* kp_block, float th, float nnratio, int far_points, float th_far, int32_t* match,
+               oracle_sbp_record* recs) {
+    SbpState st;
+    st.blocked.assign(n, 0);
+    if (kp_block) std::copy(kp_block, kp_block + n, st.blocked.begin());
+    st.blk0 = kp_block;
+    st.match = match;
+    for (int k = 0; k < n; ++k) match[k] = -1;
+    const bool bFactor = th != 1.0;
+    const int nl = R ? R->base : n;
+    int nmatches = 0;
+    for (int i = 0; i < nmp; ++i) {
+        const oracle_map_point& mp = mps[i];
+        oracle_sbp_record* rl = recs ? recs + 2 * (size_t)i : nullptr;
+        oracle_sbp_record* rr = recs && R ? rl + 1 : nullptr;
+        for (oracle_sbp_record* r : {rl, recs ? rl + 1 : nullptr})
+            if (r) *r = oracle_sbp_record{ORACLE_SBP_NO_WINDOW, 0, 0, 0, 0, {-1, -1}};
+        auto stop = [&](int code) {
+            if (rl) rl->code = code;
+            if (rr) rr->code = code;
+        };
+        if (!(mp.flags & ORACLE_MP_IN_VIEW) && !(R && (mp.flags & ORACLE_MP_IN_VIEW_R))) {
+            stop(ORACLE_SBP_NOT_IN_VIEW);
+            continue;
+        }
+        if (far_points && mp.depth > th_far) {
+            stop(ORACLE_SBP_FAR);
+            continue;
+        }
+        if (recs && far_points && mp.depth == th_far) {
+            rl->flags |= ORACLE_SBP_F_FAR_EQ;
+            if (rr) rr->flags |= ORACLE_SBP_F_FAR_EQ;
+        }
+        if (mp.flags & ORACLE_MP_BAD) {
+            stop(ORACLE_SBP_BAD);
+            continue;
+        }
+        int leftPartner = -1, leftBest = -1;
+        if (rr) rr->code = (mp.flags & ORACLE_MP_IN_VIEW_R) ? ORACLE_SBP_SKIPPED : ORACLE_SBP_NOT_IN_VIEW;
+        if (!(mp.flags & ORACLE_MP_IN_VIEW)) {
+            if (rl) rl->code = ORACLE_SBP_NOT_IN_VIEW;
+        } else {
+            const int lvl = mp.level;
+            if (lvl < 0 || lvl >= nlevels) {  // PredictScale never leaves [0, nlevels)
+                if (rl) rl->code = ORACLE_SBP_LEVEL_RANGE;
+                if (!R) continue;
+            } else {
+                float r = mp.view_cos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (:216-222)
+                if (bFactor) r *= th;
+                const int w = sbp_window(L, bounds, mp, mp.proj_x, mp.proj_y, r * scale[lvl], lvl, false, nnratio, st,
+                                         rl, &leftBest);
+                if (w == SBP_RATIO) {  // the `continue` of :129 skips the right window too
+                    if (rl && R && (mp.flags & ORACLE_MP_IN_VIEW_R)) rl->flags |= ORACLE_SBP_F_SKIPPED_RIGHT;
+                    continue;
+                }
+                if (w == SBP_ACCEPT) {
+                    sbp_assign(st, leftBest, i, mp, rl, 0);
+                    if (R && l2r && l2r[leftBest] != -1) {
+                        leftPartner = l2r[leftBest];
+                        if (rl) rl->flags |= ORACLE_SBP_F_PARTNER;
+                        sbp_assign(st, leftPartner + nl, i, mp, rl, 1);
+                        nmatches++;
+                    }
+                    nmatches++;
+                }
+            }
+        }
+        if (R && (mp.flags & ORACLE_MP_IN_VIEW_R)) {
+            const int lvl = mp.level_r;
+            if (lvl == -1 || lvl < 0 || lvl >= nlevels) {
+                if (rr) rr->code = lvl == -1 ? ORACLE_SBP_LEVEL_R_M1 : ORACLE_SBP_LEVEL_RANGE;
+                continue;
+            }
+            const float r = mp.view_cos_r > 0.998 ? 2.5f : 4.0f;  // no th factor (:150)
+            int bestIdx = -1;
+            const int w = sbp_window(*R, bounds, mp, mp.proj_xr, mp.proj_yr, r * scale[lvl], lvl, true, nnratio, st,
+                                     rr, &bestIdx);
+            if (w != SBP_ACCEPT) continue;
+            if (rr && bestIdx == leftPartner) rr->flags |= ORACLE_SBP_F_OWN_PARTNER;
+            if (r2l && r2l[bestIdx] != -1) {
+                if (rr) rr->flags |= ORACLE_SBP_F_PARTNER;
+                sbp_assign(st, r2l[bestIdx], i, mp, rr, 0);
+                nmatches++;
+            }
+            sbp_assign(st, bestIdx + nl, i, mp, rr, 1);
+            nmatches++;
+            if (rr) {
+                const int a[4] = {rl->assigned[0], rl->assigned[1], rr->assigned[0], rr->assigned[1]};
+                for (int p = 0; p < 4; ++p)
+                    for (int q = p + 1; q < 4; ++q)
+                        if (a[p] >= 0 && a[p] == a[q]) rr->flags |= ORACLE_SBP_F_DOUBLE_ASSIGN;
+            }
+        }
+    }
+    return nmatches;
+}
+
 }  // namespace
+
+int oracle_search_by_projection_coded(const oracle_map_point* mps, int nmp, const float* xy_un,
+                                      const int32_t* octave, const uint8_t* desc, const float* uRight, int n,
+                                      const float bounds[4], const int32_t* cell_start, const int32_t* cell_idx,
+                                      const float* scale, int nlevels, const uint8_t* kp_block, float th,
+                                      float nnratio, int far_points, float th_far, int32_t* match,
+                                      oracle_sbp_record* recs) {
+    const SbpSide L{xy_un, octave, desc, cell_start, cell_idx, uRight, 0};
+    return sbp_search(mps, nmp, L, nullptr, n, bounds, nullptr, nullptr, scale, nlevels, kp_block, th, nnratio,
+                      far_points, th_far, match, recs);
+}
 
 int oracle_search_by_projection(const oracle_map_point* mps, int nmp, const float* xy_un, const int32_t* octave,
                                 const uint8_t* desc, const float* uRight, int n, const float bounds[4],
                                 const int32_t* cell_start, const int32_t* cell_idx, const float* scale,
                                 int nlevels, const uint8_t* kp_block, float th, float nnratio,
                                 int far_points, float th_far, int32_t* match) {
-    std::vector<uint8_t> blocked(n, 0);
-    if (kp_block) std::copy(kp_block, kp_block + n, blocked.begin());
-    for (int k = 0; k < n; ++k) match[k] = -1;
-    const bool bFactor = th != 1.0;
-    std::vector<int> cand;
-    int nmatches = 0;
-    for (int i = 0; i < nmp; ++i) {
-        const oracle_map_point& mp = mps[i];
-        if (!(mp.flags & ORACLE_MP_IN_VIEW)) continue;
-        if (far_points && mp.depth > th_far) continue;
-        if (mp.flags & ORACLE_MP_BAD) continue;
-        const int lvl = mp.level;
-        if (lvl < 0 || lvl >= nlevels) continue;  // PredictScale never leaves [0, nlevels)
-        float r = mp.view_cos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (:216-222)
-        if (bFactor) r *= th;
-        const float rs = r * scale[lvl];
-        features_in_area(xy_un, octave, bounds, cell_start, cell_idx, mp.proj_x, mp.proj_y, rs, lvl - 1, lvl, cand);
-        if (cand.empty()) continue;
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int idx : cand) {
-            if (blocked[idx]) continue;
-            if (uRight && uRight[idx] > 0) {
-                const float er = std::fabs(mp.proj_xr - uRight[idx]);
-                if (er > r * scale[lvl]) continue;
-            }
-            const int dist = oracle_descriptor_distance(mp.desc, desc + (size_t)idx * 32);
-            if (dist < bestDist) {
-                bestDist2 = bestDist;
-                bestDist = dist;
-                bestLevel2 = bestLevel;
-                bestLevel = octave[idx];
-                bestIdx = idx;
-            } else if (dist < bestDist2) {
-                bestLevel2 = octave[idx];
-                bestDist2 = dist;
-            }
-        }
-        if (bestDist <= 100) {  // TH_HIGH
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-            if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                match[bestIdx] = i;
-                blocked[bestIdx] = (mp.flags & ORACLE_MP_HAS_OBS) ? 1 : 0;
-                nmatches++;
-            }
-        }
-    }
-    return nmatches;
+    return oracle_search_by_projection_coded(mps, nmp, xy_un, octave, desc, uRight, n, bounds, cell_start, cell_idx,
+                                             scale, nlevels, kp_block, th, nnratio, far_points, th_far, match,
+                                             nullptr);
+}
+
+int oracle_search_by_projection2_coded(const oracle_map_point* mps, int nmp, const float* xyL, const int32_t* octL,
+                                       const uint8_t* descL, int nl, const int32_t* csL, const int32_t* ciL,
+                                       const float* xyR, const int32_t* octR, const uint8_t* descR, int nr,
+                                       const int32_t* csR, const int32_t* ciR, const float bounds[4],
+                                       const int32_t* l2r, const int32_t* r2l, const float* scale, int nlevels,
+                                       const uint8_t* kp_block, float th, float nnratio, int far_points,
+                                       float th_far, int32_t* match, oracle_sbp_record* recs) {
+    const SbpSide L{xyL, octL, descL, csL, ciL, nullptr, 0};
+    const SbpSide R{xyR, octR, descR, csR, ciR, nullptr, nl};
+    return sbp_search(mps, nmp, L, &R, nl + nr, bounds, l2r, r2l, scale, nlevels, kp_block, th, nnratio, far_points,
+                      th_far, match, recs);
 }
 
 int oracle_search_by_projection2(const oracle_map_point* mps, int nmp, const float* xyL, const int32_t* octL,
@@ -1395,90 +1617,7 @@ int oracle_search_by_projection2(const oracle_map_point* mps, int nmp, const flo
                                  const int32_t* l2r, const int32_t* r2l, const float* scale, int nlevels,
                                  const uint8_t* kp_block, float th, float nnratio, int far_points,
                                  float th_far, int32_t* match) {
-    const int n = nl + nr;
-    std::vector<uint8_t> blocked(n, 0);  // mvpMapPoints[k] set with Observations() > 0
-    if (kp_block) std::copy(kp_block, kp_block + n, blocked.begin());
-    for (int k = 0; k < n; ++k) match[k] = -1;
-    auto assign = [&](int k, int i, const oracle_map_point& mp) {
-        match[k] = i;
-        blocked[k] = (mp.flags & ORACLE_MP_HAS_OBS) ? 1 : 0;
-    };
-    const bool bFactor = th != 1.0;
-    std::vector<int> cand;
-    int nmatches = 0;
-    for (int i = 0; i < nmp; ++i) {
-        const oracle_map_point& mp = mps[i];
-        if (!(mp.flags & ORACLE_MP_IN_VIEW) && !(mp.flags & ORACLE_MP_IN_VIEW_R)) continue;
-        if (far_points && mp.depth > th_far) continue;
-        if (mp.flags & ORACLE_MP_BAD) continue;
-        if (mp.flags & ORACLE_MP_IN_VIEW) {
-            const int lvl = mp.level;
-            if (lvl >= 0 && lvl < nlevels) {
-                float r = mp.view_cos > 0.998 ? 2.5f : 4.0f;
-                if (bFactor) r *= th;
-                features_in_area(xyL, octL, bounds, csL, ciL, mp.proj_x, mp.proj_y, r * scale[lvl], lvl - 1, lvl, cand);
-                if (!cand.empty()) {
-                    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-                    for (int idx : cand) {
-                        if (blocked[idx]) continue;
-                        const int dist = oracle_descriptor_distance(mp.desc, descL + (size_t)idx * 32);
-                        if (dist < bestDist) {
-                            bestDist2 = bestDist;
-                            bestDist = dist;
-                            bestLevel2 = bestLevel;
-                            bestLevel = octL[idx];
-                            bestIdx = idx;
-                        } else if (dist < bestDist2) {
-                            bestLevel2 = octL[idx];
-                            bestDist2 = dist;
-                        }
-                    }
-                    if (bestDist <= 100) {
-                        if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;  // skips the right branch too
-                        if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                            assign(bestIdx, i, mp);
-                            if (l2r && l2r[bestIdx] != -1) {
-                                assign(l2r[bestIdx] + nl, i, mp);
-                                nmatches++;
-                            }
-                            nmatches++;
-                        }
-                    }
-                }
-            }
-        }
-        if (mp.flags & ORACLE_MP_IN_VIEW_R) {
-            const int lvl = mp.level_r;
-            if (lvl != -1 && lvl >= 0 && lvl < nlevels) {
-                const float r = mp.view_cos_r > 0.998 ? 2.5f : 4.0f;
-                features_in_area(xyR, octR, bounds, csR, ciR, mp.proj_xr, mp.proj_yr, r * scale[lvl], lvl - 1, lvl, cand);
-                if (cand.empty()) continue;
-                int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-                for (int idx : cand) {
-                    if (blocked[idx + nl]) continue;
-                    const int dist = oracle_descriptor_distance(mp.desc, descR + (size_t)idx * 32);
-                    if (dist < bestDist) {
-                        bestDist2 = bestDist;
-                        bestDist = dist;
-                        bestLevel2 = bestLevel;
-                        bestLevel = octR[idx];
-                        bestIdx = idx;
-                    } else if (dist < bestDist2) {
-                        bestLevel2 = octR[idx];
-                        bestDist2 = dist;
-                    }
-                }
-                if (bestDist <= 100) {
-                    if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-                    if (r2l && r2l[bestIdx] != -1) {
-                        assign(r2l[bestIdx], i, mp);
-                        nmatches++;
-                    }
-                    assign(bestIdx + nl, i, mp);
-                    nmatches++;
-                }
-            }
-        }
-    }
-    return nmatches;
+    return oracle_search_by_projection2_coded(mps, nmp, xyL, octL, descL, nl, csL, ciL, xyR, octR, descR, nr, csR, ciR,
+                                              bounds, l2r, r2l, scale, nlevels, kp_block, th, nnratio, far_points,
+                                              th_far, match, nullptr);
 }

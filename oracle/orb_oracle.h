@@ -200,6 +200,79 @@ int oracle_search_by_projection2(const oracle_map_point* mps, int nmp, const flo
                                  const uint8_t* kp_block, float th, float nnratio, int far_points,
                                  float th_far, int32_t* match);
 
+// The coded forms: the same matches and nmatches (the plain entry points call them with
+// recs == NULL), plus two records per map point, recs[2 * i] for the left (or only) window and
+// recs[2 * i + 1] for the right one.  A record holds the first rule that stopped the window or how
+// it was accepted (code), what the search met on the way (flags) and what a speculative replay of
+// the loop needs to know (reference semantics only; no kernel constant enters):
+//   ncand        candidates of the window under the occupancy that held before the call
+//                (kp_block), after the level, distance and mvuRight tests
+//   rank_best / rank_second   where the chosen best and second stand in the (distance, window
+//                position) order of those candidates; ncand for one that is not among them (none
+//                chosen, or a keypoint occupied before the call and freed since)
+//   assigned     the keypoints this window assigned, in order (left: best, its partner + nl;
+//                right: the partner of best, best + nl), -1 where none
+// The record is not tied to this search: another window search can fill the same fields.
+typedef struct {
+    int32_t code;   // ORACLE_SBP_*
+    int32_t flags;  // ORACLE_SBP_F_*
+    int32_t ncand, rank_best, rank_second;
+    int32_t assigned[2];
+} oracle_sbp_record;
+enum {
+    ORACLE_SBP_NO_WINDOW = 0,     // the right-window record of a pinhole frame
+    ORACLE_SBP_NOT_IN_VIEW = 1,   // mbTrackInView (left) / mbTrackInViewR (right) not set
+    ORACLE_SBP_FAR = 2,           // bFarPoints && mTrackDepth > thFarPoints
+    ORACLE_SBP_BAD = 3,           // isBad()
+    ORACLE_SBP_LEVEL_RANGE = 4,   // the predicted level outside [0, nlevels)
+    ORACLE_SBP_LEVEL_R_M1 = 5,    // mnTrackScaleLevelR == -1
+    ORACLE_SBP_EXIT_MINX = 6,     // GetFeaturesInArea: nMinCellX >= FRAME_GRID_COLS
+    ORACLE_SBP_EXIT_MAXX = 7,     //                    nMaxCellX < 0
+    ORACLE_SBP_EXIT_MINY = 8,     //                    nMinCellY >= FRAME_GRID_ROWS
+    ORACLE_SBP_EXIT_MAXY = 9,     //                    nMaxCellY < 0
+    ORACLE_SBP_NO_KEYPOINT = 10,  // vIndices.empty()
+    ORACLE_SBP_ALL_TAKEN = 11,    // every candidate occupied or failed the mvuRight test
+    ORACLE_SBP_TH_HIGH = 12,      // bestDist > TH_HIGH
+    ORACLE_SBP_RATIO = 13,        // same levels and bestDist > mfNNratio * bestDist2
+    ORACLE_SBP_ACCEPT_LEVELS = 14,  // accepted: best and second on different levels
+    ORACLE_SBP_ACCEPT_RATIO = 15,   // accepted by the ratio test
+    ORACLE_SBP_SKIPPED = 16       // the right window the left ratio test's `continue` skipped
+};
+enum {
+    ORACLE_SBP_F_TIE_BEST = 1 << 0,         // two or more live candidates at the best distance
+    ORACLE_SBP_F_BEST_EQ_SECOND = 1 << 1,   // bestDist == bestDist2 (< 256)
+    ORACLE_SBP_F_BD_100 = 1 << 2,           // bestDist == TH_HIGH
+    ORACLE_SBP_F_RATIO_EQ = 1 << 3,         // same levels and bestDist == mfNNratio * bestDist2
+    ORACLE_SBP_F_EDGE = 1 << 4,             // a keypoint of the right levels with |dx| or |dy| == r
+    ORACLE_SBP_F_URIGHT_REJECT = 1 << 5,    // a candidate dropped by the mvuRight test
+    ORACLE_SBP_F_URIGHT_EQ = 1 << 6,        // |proj_xr - mvuRight| == r
+    ORACLE_SBP_F_FAR_EQ = 1 << 7,           // bFarPoints && mTrackDepth == thFarPoints
+    ORACLE_SBP_F_CLIPPED = 1 << 8,          // the cell range was clamped to the grid
+    ORACLE_SBP_F_CELL_INT = 1 << 9,         // one of the four cell-range products is an integer
+    ORACLE_SBP_F_TAKEN_SKIP = 1 << 10,      // a window keypoint skipped: taken earlier in this call
+    ORACLE_SBP_F_OVERWROTE = 1 << 11,       // assigned a keypoint that held a match of this call
+    ORACLE_SBP_F_PARTNER = 1 << 12,         // the stereo partner of best was assigned too
+    ORACLE_SBP_F_FREED_INCALL = 1 << 13,    // no observations: freed a keypoint taken in this call
+    ORACLE_SBP_F_FREED_PRECALL = 1 << 14,   // the same for a keypoint occupied before the call
+    ORACLE_SBP_F_OWN_PARTNER = 1 << 15,     // right best == the partner of this point's left match
+    ORACLE_SBP_F_DOUBLE_ASSIGN = 1 << 16,   // this point assigned one keypoint twice
+    ORACLE_SBP_F_SKIPPED_RIGHT = 1 << 17,   // (left, code RATIO) a pending right window was skipped
+    ORACLE_SBP_F_TIE_SECOND = 1 << 18       // two or more live candidates at bestDist2 > bestDist
+};
+int oracle_search_by_projection_coded(const oracle_map_point* mps, int nmp, const float* xy_un,
+                                      const int32_t* octave, const uint8_t* desc, const float* uRight, int n,
+                                      const float bounds[4], const int32_t* cell_start, const int32_t* cell_idx,
+                                      const float* scale, int nlevels, const uint8_t* kp_block, float th,
+                                      float nnratio, int far_points, float th_far, int32_t* match,
+                                      oracle_sbp_record* recs);
+int oracle_search_by_projection2_coded(const oracle_map_point* mps, int nmp, const float* xyL, const int32_t* octL,
+                                       const uint8_t* descL, int nl, const int32_t* csL, const int32_t* ciL,
+                                       const float* xyR, const int32_t* octR, const uint8_t* descR, int nr,
+                                       const int32_t* csR, const int32_t* ciR, const float bounds[4],
+                                       const int32_t* l2r, const int32_t* r2l, const float* scale, int nlevels,
+                                       const uint8_t* kp_block, float th, float nnratio, int far_points,
+                                       float th_far, int32_t* match, oracle_sbp_record* recs);
+
 // Frame::ComputeStereoFishEyeMatches (Frame.cc:1142-1201) on one frame's stereo-row kNN2
 // (orb_fisheye.cpp; parity unpinned, see there).  idx1 / dist1: [nL - monoL]; cam*: KannalaBrandt8
 // mvParameters; R12 row-major (mRlr), t12 (mtlr); sigma2: mvLevelSigma2.  Outputs: l2r [nL],

@@ -6,6 +6,10 @@ GPU: k_sbp_candidates + k_sbp_resolve against the oracle, bit-exact on every key
 map point and on nmatches -- mono and stereo (mvuRight) frames, th != 1, far-point culling,
 pre-occupied keypoints, many map points competing for the same keypoints.
 
+The coded restatement at the end (_py_sbp_coded: decision codes, flags, replay ranks, and named
+mutants of every boundary) is what tests/test_sbp_reach.py holds the coded oracle against on the
+directed map-point sets of tests/sbp_maps.py.
+
 Parity status: unpinned against the reference itself (ORBmatcher.cc needs the SLAM stack and
 OpenCV; no fixtures ship for it) -- cross-checked restatements only."""
 import math
@@ -179,8 +183,12 @@ def test_gpu_search_by_projection_bit_exact(oracle, stereo, th, far, blocked):
 
 @pytest.mark.gpu
 def test_gpu_search_by_projection_dense_conflicts(oracle):
-    """8000 map points on one frame, most competing for a few hundred keypoints: the resolve
-    pass's top-4 runs dry and re-walks windows."""
+    """8000 map points on one frame, aimed at 200 of its keypoints.  What that reaches, counted
+    with the coded oracle: 437 matches; 4890 points find every candidate of their window taken and
+    1057 find no keypoint in it (5947 with no live candidate at all); 5364 skip a keypoint taken
+    earlier in the call.  Only 2 windows hold more than four candidates, and the four-slot list runs
+    dry with more behind it -- the case that walks the window again -- once.  The dry lists, the
+    stale lanes and the frees have directed sets in tests/sbp_maps.py (tests/test_sbp_reach.py)."""
     import orbslam3lib_amd as og
     L, R = synth.stereo_pair(480, 640, 60)
     be = og.BatchExtractor(2000, 1.2, 8, 20, 7, width=640, height=480, max_images=2)
@@ -408,3 +416,234 @@ def test_gpu_search_by_projection_1080p_large_lds(oracle):
     gm1, gnm1 = be.projection_matches(0)
     np.testing.assert_array_equal(gm1, m1)
     assert gnm1 == nm1
+
+
+# ---- the coded restatement: decision codes, flags and replay ranks of both forms ---------------
+# oracle.search_by_projection_coded / search_by_projection2_coded restated from ORBmatcher.cc:44-214
+# and Frame.cc:673-735 (record layout: orb_oracle.h).  `mut` names comparisons to get wrong on
+# purpose: tests/test_sbp_reach.py asserts that each such mutant disagrees with the oracle on the
+# map-point sets of tests/sbp_maps.py.
+MUTANTS = ("far_ge", "cos_float", "floor_trunc", "ceil_trunc", "exit_minx_gt", "exit_maxx_le", "exit_miny_gt",
+           "exit_maxy_le", "octave_lo_le", "octave_hi_ge", "edge_x_le", "edge_y_le", "uright_ge", "best_le",
+           "second_le", "th_high_99", "ratio_ge", "level_lo_le", "level_hi_m1", "level_r_lo_le", "level_r_hi_m1")
+_POP = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.int64)
+
+
+def _py_area_coded(S, bounds, x, y, rs, lvl, mut):
+    """GetFeaturesInArea(x, y, rs, lvl - 1, lvl) -> (indices in window order, exit 0..4, flags)."""
+    from oracle import oracle_py as O
+    xy, octv, _, cs, ci = S
+    wi = F32(F32(64) / F32(bounds[1] - bounds[0]))
+    hi = F32(F32(48) / F32(bounds[3] - bounds[2]))
+    trunc = lambda v: math.trunc(float(v))
+    fl = trunc if "floor_trunc" in mut else math.floor
+    ce = trunc if "ceil_trunc" in mut else math.ceil
+    p0 = F32(F32(F32(x - bounds[0]) - rs) * wi)
+    x0 = max(0, int(fl(p0)))
+    if x0 > 64 or (x0 == 64 and "exit_minx_gt" not in mut):
+        return [], 1, 0
+    p1 = F32(F32(F32(x - bounds[0]) + rs) * wi)
+    x1 = min(63, int(ce(p1)))
+    if x1 < 0 or (x1 == 0 and "exit_maxx_le" in mut):
+        return [], 2, 0
+    p2 = F32(F32(F32(y - bounds[2]) - rs) * hi)
+    y0 = max(0, int(fl(p2)))
+    if y0 > 48 or (y0 == 48 and "exit_miny_gt" not in mut):
+        return [], 3, 0
+    p3 = F32(F32(F32(y - bounds[2]) + rs) * hi)
+    y1 = min(47, int(ce(p3)))
+    if y1 < 0 or (y1 == 0 and "exit_maxy_le" in mut):
+        return [], 4, 0
+    flags = 0
+    if fl(p0) < 0 or ce(p1) > 63 or fl(p2) < 0 or ce(p3) > 47:
+        flags |= O.SBPF_CLIPPED
+    if any(float(p) == math.floor(float(p)) for p in (p0, p1, p2, p3)):
+        flags |= O.SBPF_CELL_INT
+    lo, hi_ = lvl - 1, lvl
+    out = []
+    for ix in range(x0, x1 + 1):
+        for iy in range(y0, min(y1, 47) + 1):
+            for k in ci[cs[ix * 48 + iy]:cs[ix * 48 + iy + 1]]:
+                o = octv[k]
+                if o < lo or (o == lo and "octave_lo_le" in mut) or o > hi_ or (o == hi_ and "octave_hi_ge" in mut):
+                    continue
+                dx, dy = abs(F32(xy[k, 0] - x)), abs(F32(xy[k, 1] - y))
+                if dx == rs or dy == rs:
+                    flags |= O.SBPF_EDGE
+                if (dx < rs or (dx == rs and "edge_x_le" in mut)) and (dy < rs or (dy == rs and "edge_y_le" in mut)):
+                    out.append(int(k))
+    return out, 0, flags
+
+
+def _py_window_coded(S, base, bounds, mp, x, y, rs, lvl, uright, right, nnratio, st, rec, mut):
+    """One window up to its decision -> ("none" | "ratio" | "accept", best keypoint)."""
+    from oracle import oracle_py as O
+    blocked, blk0, match = st
+    octv, desc = S[1], S[2]
+    cand, ex, fl = _py_area_coded(S, bounds, x, y, rs, lvl, mut)
+    rec["flags"] |= fl
+    if not cand:
+        rec["code"] = O.SBP_EXIT_MINX + ex - 1 if ex else O.SBP_NO_KEYPOINT
+        return "none", -1
+    best, second = (256, -1, -1), (256, -1, -1)  # distance, level, keypoint
+    pre, live = [], []
+    for k in cand:
+        taken, was_free = bool(blocked[base + k]), not blk0[base + k]
+        if taken and match[base + k] != -1:
+            rec["flags"] |= O.SBPF_TAKEN_SKIP
+        if taken and not was_free:
+            continue
+        if uright is not None and uright[k] > 0:
+            er = abs(F32(mp["proj_xr"] - uright[k]))
+            if er == rs:
+                rec["flags"] |= O.SBPF_URIGHT_EQ
+            if er > rs or (er == rs and "uright_ge" in mut):
+                rec["flags"] |= O.SBPF_URIGHT_REJECT
+                continue
+        d = int(_POP[mp["desc"] ^ desc[k]].sum())
+        if was_free:
+            pre.append((d, k))
+        if taken:
+            continue
+        live.append(d)
+        if d < best[0] or (d == best[0] and "best_le" in mut):
+            second, best = best, (d, int(octv[k]), k)
+        elif d < second[0] or (d == second[0] and "second_le" in mut):
+            second = (d, int(octv[k]), k)
+    ranked = [k for _, k in sorted(pre, key=lambda c: c[0])]  # stable: (distance, window position)
+    rec["ncand"] = len(ranked)
+    rec["rank_best"] = ranked.index(best[2]) if best[2] in ranked else len(ranked)
+    rec["rank_second"] = ranked.index(second[2]) if second[2] in ranked else len(ranked)
+    (bd, bl, bi), (sd, sl, _) = best, second
+    if live.count(bd) > 1:
+        rec["flags"] |= O.SBPF_TIE_BEST
+    if bd < sd < 256 and live.count(sd) > 1:
+        rec["flags"] |= O.SBPF_TIE_SECOND
+    if bd < 256 and bd == sd:
+        rec["flags"] |= O.SBPF_BEST_EQ_SECOND
+    if bd == 100:
+        rec["flags"] |= O.SBPF_BD_100
+    if bd > (99 if "th_high_99" in mut else 100):
+        rec["code"] = O.SBP_ALL_TAKEN if bi < 0 else O.SBP_TH_HIGH
+        return "none", -1
+    prod = F32(F32(nnratio) * F32(sd))
+    if bl == sl and F32(bd) == prod:
+        rec["flags"] |= O.SBPF_RATIO_EQ
+    if bl == sl and (F32(bd) > prod or (F32(bd) == prod and "ratio_ge" in mut)):
+        rec["code"] = O.SBP_RATIO
+        return "ratio", -1
+    rec["code"] = O.SBP_ACCEPT_LEVELS if bl != sl else O.SBP_ACCEPT_RATIO
+    return "accept", bi
+
+
+def _py_sbp_coded(mps, L, R, bounds, uright, l2r, r2l, blk, th, nnratio, far, th_far, scale, nlevels,
+                  mut=frozenset()):
+    """Both forms (R None: a pinhole frame, else the two-camera one) -> (match, nmatches, records
+    [nmp, 2] of oracle.SBP_RECORD_DTYPE).  L / R = (xy, octave, desc, cell_start, cell_idx)."""
+    from oracle import oracle_py as O
+    mut = frozenset(mut)
+    assert mut <= set(MUTANTS), mut
+    nl = len(L[1])
+    n = nl + (len(R[1]) if R is not None else 0)
+    blk0 = np.zeros(n, bool) if blk is None else np.asarray(blk[:n]).astype(bool)
+    blocked, match = blk0.copy(), np.full(n, -1, np.int32)
+    st = (blocked, blk0, match)
+    recs = np.zeros((len(mps), 2), O.SBP_RECORD_DTYPE)
+    recs["assigned"] = -1
+    nm = 0
+    two = R is not None
+
+    def assign(k, i, obs, rec, slot):
+        if match[k] != -1:
+            rec["flags"] |= O.SBPF_OVERWROTE
+        if not obs and blocked[k]:
+            rec["flags"] |= O.SBPF_FREED_INCALL if match[k] != -1 else O.SBPF_FREED_PRECALL
+        rec["assigned"][slot] = k
+        match[k], blocked[k] = i, obs
+    for i, mp in enumerate(mps):
+        rl = dict(code=O.SBP_NO_WINDOW, flags=0, ncand=0, rank_best=0, rank_second=0, assigned=[-1, -1])
+        rr = dict(rl, assigned=[-1, -1])
+        try:
+            flags, obs = int(mp["flags"]), bool(mp["flags"] & 4)
+            in_l, in_r = bool(flags & 1), two and bool(flags & 8)
+            stop = None
+            if not in_l and not in_r:
+                stop = O.SBP_NOT_IN_VIEW
+            elif far and (mp["depth"] > F32(th_far) or (mp["depth"] == F32(th_far) and "far_ge" in mut)):
+                stop = O.SBP_FAR
+            else:
+                if far and mp["depth"] == F32(th_far):
+                    rl["flags"] |= O.SBPF_FAR_EQ
+                    if two:
+                        rr["flags"] |= O.SBPF_FAR_EQ
+                if flags & 2:
+                    stop = O.SBP_BAD
+            if stop is not None:
+                rl["code"] = stop
+                if two:
+                    rr["code"] = stop
+                continue
+            if two:
+                rr["code"] = O.SBP_SKIPPED if in_r else O.SBP_NOT_IN_VIEW
+            left_partner = -1
+            if not in_l:
+                rl["code"] = O.SBP_NOT_IN_VIEW
+            else:
+                lvl = int(mp["level"])
+                if lvl < 0 or (lvl == 0 and "level_lo_le" in mut) or lvl >= nlevels - ("level_hi_m1" in mut):
+                    rl["code"] = O.SBP_LEVEL_RANGE
+                    if not two:
+                        continue
+                else:
+                    if "cos_float" in mut:
+                        r = F32(2.5) if F32(mp["view_cos"]) > F32(0.998) else F32(4.0)
+                    else:
+                        r = F32(2.5) if float(mp["view_cos"]) > 0.998 else F32(4.0)
+                    if F32(th) != 1.0:
+                        r = F32(r * F32(th))
+                    w, bi = _py_window_coded(L, 0, bounds, mp, F32(mp["proj_x"]), F32(mp["proj_y"]),
+                                             F32(r * F32(scale[lvl])), lvl, uright, False, nnratio, st, rl, mut)
+                    if w == "ratio":
+                        if in_r:
+                            rl["flags"] |= O.SBPF_SKIPPED_RIGHT
+                        continue
+                    if w == "accept":
+                        assign(bi, i, obs, rl, 0)
+                        if two and l2r is not None and l2r[bi] != -1:
+                            left_partner = int(l2r[bi])
+                            rl["flags"] |= O.SBPF_PARTNER
+                            assign(nl + left_partner, i, obs, rl, 1)
+                            nm += 1
+                        nm += 1
+            if in_r:
+                lvl = int(mp["level_r"])
+                if lvl == -1:
+                    rr["code"] = O.SBP_LEVEL_R_M1
+                    continue
+                if lvl < 0 or (lvl == 0 and "level_r_lo_le" in mut) or lvl >= nlevels - ("level_r_hi_m1" in mut):
+                    rr["code"] = O.SBP_LEVEL_RANGE
+                    continue
+                if "cos_float" in mut:
+                    r = F32(2.5) if F32(mp["view_cos_r"]) > F32(0.998) else F32(4.0)
+                else:
+                    r = F32(2.5) if float(mp["view_cos_r"]) > 0.998 else F32(4.0)
+                w, bi = _py_window_coded(R, nl, bounds, mp, F32(mp["proj_xr"]), F32(mp["proj_yr"]),
+                                         F32(r * F32(scale[lvl])), lvl, None, True, nnratio, st, rr, mut)
+                if w != "accept":
+                    continue
+                if bi == left_partner:
+                    rr["flags"] |= O.SBPF_OWN_PARTNER
+                if r2l is not None and r2l[bi] != -1:
+                    rr["flags"] |= O.SBPF_PARTNER
+                    assign(int(r2l[bi]), i, obs, rr, 0)
+                    nm += 1
+                assign(nl + bi, i, obs, rr, 1)
+                nm += 1
+                a = [v for v in rl["assigned"] + rr["assigned"] if v >= 0]
+                if len(set(a)) < len(a):
+                    rr["flags"] |= O.SBPF_DOUBLE_ASSIGN
+        finally:
+            for wdx, rec in enumerate((rl, rr)):
+                for key, val in rec.items():
+                    recs[key][i, wdx] = val
+    return match, nm, recs
