@@ -449,8 +449,7 @@ int orbgpu_download_initialization_matches(orbgpu_ctx* ctx, int pair, int32_t* m
  * ends up in vpMapPointMatches[k], -1 if none; *n_kp = F.N; *nmatches = the reference's return
  * value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when check_orientation ==
  * 0).  Errors as for orbgpu_download_initialization_matches.
- * SearchByBoW on two-camera frames (F.Nleft != -1, :297-324 and :358-387) and SearchByBoW(KeyFrame*,
- * KeyFrame*) are not built. */
+ * SearchByBoW on two-camera frames (F.Nleft != -1, :297-324 and :358-387) is not built. */
 typedef struct {
     uint8_t desc[32];  /* pKF->mDescriptors.row(i) */
     float angle;       /* pKF->mvKeysUn[i].angle */
@@ -466,6 +465,89 @@ int orbgpu_search_by_bow_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* fram
                                int check_orientation, void* stream);
 int orbgpu_download_bow_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int cap, int* n_kp,
                                 int* nmatches, int32_t rot_hist[30]);
+
+/* ---- ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) ----------
+ * The matcher LocalMapping::CreateNewMapPoints runs for the new keyframe against each of its 10 (30
+ * when monocular) neighbours (LocalMapping.cc:397-472): cpp/src/ORBmatcher.cc:908-1153 with
+ * Pinhole::epipolarConstrain (CameraModels/Pinhole.cpp:102-124) and ComputeThreeMaxima :2061-2102,
+ * on pinhole keyframes (pKF1->mpCamera2 == nullptr, NLeft == -1).  Pair p = keyframe 1, which is
+ * image frames[p] of the last batch, inside the range of the last orbgpu_undistort_grid_batch (its
+ * positions are mvKeysUn), against keyframe 2, given by the host as kf_pts [kf_offsets[p],
+ * kf_offsets[p + 1]); several pairs may name the same frame.  The vocabulary stays on the host: the
+ * node of each keypoint (mFeatVec) is an input on both sides.  F12 and the epipole are inputs per
+ * pair: the reference recomputes F12 per candidate with Eigen's 3x3 inverses (Pinhole.cpp:104-107),
+ * which does not vary over a pinhole pair, so the host evaluates that expression once.  The level
+ * tables mvScaleFactors / mvLevelSigma2 of both keyframes are the context's: both keyframes are
+ * assumed to come from the same extractor settings.  All arithmetic is IEEE single, evaluated in the
+ * reference's order, unless a step says otherwise:
+ *   1. match12 has keyframe 1's N1 entries, all -1 (:957).
+ *   2. only the nodes present in both feature vectors are visited (:970-1119); nodes do not
+ *      interact; a node's list holds keypoint indices in ascending order.
+ *   3. in a common node, for idx1 ascending (:974): a keypoint 1 with ORBGPU_TRI_HAS_POINT is skipped
+ *      (:978-984), and with only_stereo one without ORBGPU_TRI_STEREO (:986-990).
+ *   4. bestDist = TH_LOW = 50, bestIdx2 = -1 (:1001-1002); for idx2 ascending (:1004) a candidate
+ *      continues when it has ORBGPU_TRI_HAS_POINT (:1008-1012; vbMatched2 is never set, and there is no
+ *      isBad test here), when only_stereo is on and it lacks ORBGPU_TRI_STEREO (:1014-1018), when
+ *      dist > 50 || dist > bestDist (:1024: an equal distance does not continue, so the later
+ *      candidate replaces the earlier one), when both keypoints are mono and, with dx = ep[0] - x2,
+ *      dy = ep[1] - y2, dx * dx + dy * dy < 100 * mvScaleFactors[octave2] (:1033-1041, an int *
+ *      float product), or when coarse is off and the epipolar test fails (:1079); otherwise it
+ *      becomes the best (:1081-1082).
+ *   5. the epipolar test (Pinhole.cpp:110-123): a = x1 * F(0,0) + y1 * F(1,0) + F(2,0) left to right,
+ *      b with column 1, c with column 2; num = a * x2 + b * y2 + c; den = a * a + b * b; false when
+ *      den == 0; else (double)(num * num / den) < 3.84 * (double)mvLevelSigma2[octave2]: 3.84 is a
+ *      double literal, so the product and the comparison are in double.  sigmaLevel is unused.  A NaN
+ *      num * num / den fails, as in the reference.
+ *   6. when bestIdx2 >= 0: match12[idx1] = bestIdx2, nmatches++ (:1086-1092); with check_orientation
+ *      rot = angle1 - angle2 (+360 if negative), bin = round(rot * (1.0f / 30)) (30 -> 0), no fmodf
+ *      (:1094-1104).  One keypoint 2 may end up matched by several keypoints 1: that is the reference's
+ *      behaviour and it is kept.
+ *   7. ComputeThreeMaxima on the 30 bin sizes; every entry of a bin outside the three maxima is
+ *      cleared and takes one off nmatches (:1121-1140).
+ * Deviations: a negative node means "this keypoint is in no node"; an event whose bin falls outside
+ * [0, 30) (the reference asserts) counts in nmatches, enters no bin and cannot be rejected.  Parity
+ * with the reference is unpinned, as for the other matcher functions: the yardstick is the Python
+ * restatement in tests/test_search_for_triangulation.py.
+ * f_nodes: [n_pairs][node_stride], the node of keypoint k of pair p's keyframe 1 at [p][k]; f_flags:
+ * [n_pairs][flag_stride] u8 with the two flag bits for that keypoint, NULL: no map points and no
+ * stereo keypoints.  Host arrays are pageable and may be reused when the call returns.
+ * ORBGPU_ERR_INVALID: null context, n_pairs < 0 or above the context's image capacity, null arrays
+ * when n_pairs > 0, a frame outside the gridded range, kf_offsets not ascending from a value >= 0, a
+ * stride below a frame's keypoint count, an octave of a keyframe point outside [0, nlevels); n_pairs ==
+ * 0 succeeds and leaves no pair to download.  ORBGPU_ERR_CAPACITY when a side holds more than
+ * ORBGPU_BOW_MAX_POINTS keypoints (the context's keypoint capacity per image counts for keyframe 1).
+ * Every status is decided before any launch.
+ * orbgpu_download_triangulation_matches: match12[k] = the index, within the pair's keyframe points,
+ * that the reference leaves in vMatches12[k], -1 if none; *n1 = N1; *nmatches = the reference's
+ * return value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when
+ * check_orientation == 0).  vMatchedPairs is the list of (k, match12[k]) over the non-negative
+ * entries, k ascending (:1142-1150).  Errors as for orbgpu_download_bow_matches.
+ * Not built: the two-camera SearchForTriangulation (mpCamera2 set: the Tll / Tlr / Trl / Trr
+ * selection :1043-1077 and KannalaBrandt8::epipolarConstrain, which triangulates), SearchByBoW(KeyFrame*,
+ * KeyFrame*), Fuse and the Sim3 searches (SearchBySim3, the Sim3 SearchByProjection overloads). */
+typedef struct {
+    uint8_t desc[32];  /* pKF2->mDescriptors.row(i) */
+    float x, y;        /* pKF2->mvKeysUn[i].pt */
+    float angle;       /* pKF2->mvKeysUn[i].angle */
+    int32_t octave;    /* pKF2->mvKeysUn[i].octave */
+    int32_t node;      /* the node of mFeatVec that holds i; < 0: none */
+    int32_t flags;     /* ORBGPU_TRI_HAS_POINT: pKF2->GetMapPoint(i) != nullptr (no isBad test here, :1008-1012)
+                          ORBGPU_TRI_STEREO:    pKF2->mvuRight[i] >= 0 */
+} orbgpu_triang_point;   /* 56 bytes */
+#define ORBGPU_TRI_HAS_POINT 1
+#define ORBGPU_TRI_STEREO 2
+typedef struct {
+    float F12[9];      /* row-major, K1^-T * [t12]x * R12 * K2^-1 as Pinhole.cpp:104-107 computes it */
+    float ep[2];       /* pKF2->mpCamera->project(T2w * Cw1) (:925-927) */
+} orbgpu_triang_pair;    /* 44 bytes */
+
+int orbgpu_search_for_triangulation_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames,
+                                          const orbgpu_triang_point* kf_pts, const int32_t* kf_offsets,
+                                          const orbgpu_triang_pair* pairs, const int32_t* f_nodes,
+                                          int node_stride, const uint8_t* f_flags, int flag_stride,
+                                          int only_stereo, int coarse, int check_orientation, void* stream);
+int orbgpu_download_triangulation_matches(orbgpu_ctx* ctx, int pair, int32_t* match12, int cap, int* n1,
+                                          int* nmatches, int32_t rot_hist[30]);
 
 /* ---- ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) ----
  * The search Tracking::Relocalization (Tracking.cc:3670-3829) runs on a candidate keyframe when PnP

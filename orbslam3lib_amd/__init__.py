@@ -19,7 +19,8 @@ import os
 import numpy as np
 
 __all__ = ["ORBextractor", "ORBmatcher", "BFMatcher", "BatchExtractor", "KEYPOINT_DTYPE", "MAP_POINT_DTYPE",
-           "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "RELOC_POINT_DTYPE", "RELOC_POSE_DTYPE", "predict_scale_table",
+           "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "RELOC_POINT_DTYPE", "RELOC_POSE_DTYPE", "TRIANG_POINT_DTYPE",
+           "TRIANG_PAIR_DTYPE", "predict_scale_table",
            "OrbGpuError", "load_library", "LIB_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -44,6 +45,12 @@ TRACK_RIG_DTYPE = np.dtype([("cam_left", "<f4", (8,)), ("Rrl", "<f4", (9,)), ("t
 BOW_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("angle", "<f4"), ("node", "<i4"), ("flags", "<i4")])
 BOW_HAS_POINT = 1  # ORBGPU_BOW_HAS_POINT
 BOW_MAX_POINTS = 8192  # ORBGPU_BOW_MAX_POINTS
+# orbgpu_triang_point (56 B): a keypoint of keyframe 2 for search_for_triangulation; orbgpu_triang_pair
+# (44 B): the pair's F12 (row-major) and the epipole in keyframe 2
+TRIANG_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"),
+                               ("octave", "<i4"), ("node", "<i4"), ("flags", "<i4")])
+TRIANG_PAIR_DTYPE = np.dtype([("F12", "<f4", (9,)), ("ep", "<f4", (2,))])
+TRI_HAS_POINT, TRI_STEREO = 1, 2  # ORBGPU_TRI_HAS_POINT, ORBGPU_TRI_STEREO
 # orbgpu_reloc_point (60 B): a keyframe's map point for reloc_by_projection; orbgpu_reloc_pose (60 B):
 # CurrentFrame.GetPose(), row-major, and its camera centre Tcw.inverse().translation()
 RELOC_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("min_distance", "<f4"),
@@ -76,6 +83,7 @@ EXPORTED = [
     "orbgpu_track_by_projection_stereo", "orbgpu_search_for_initialization_batch",
     "orbgpu_download_initialization_matches", "orbgpu_search_by_bow_batch", "orbgpu_download_bow_matches",
     "orbgpu_reloc_by_projection_batch", "orbgpu_download_reloc_matches", "orbgpu_predict_scale_table",
+    "orbgpu_search_for_triangulation_batch", "orbgpu_download_triangulation_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -859,6 +867,42 @@ class BatchExtractor:
         the point that ends up in vpMapPointMatches, -1 if none; nmatches; rot_hist [30] int32: the
         bin sizes before the three-maxima rule) of pair `pair` of the last search_by_bow."""
         return self._download_matches(_lib.orbgpu_download_bow_matches, pair, cap)
+
+    def search_for_triangulation(self, frames, kf_points, pairs, f_nodes, f_flags=None, only_stereo=False,
+                                 coarse=False, check_orientation=False, stream=None):
+        """ORBmatcher(nnratio, check_orientation).SearchForTriangulation(pKF1, pKF2, vMatchedPairs,
+        bOnlyStereo, bCoarse) (ORBmatcher.cc:908-1153, LocalMapping::CreateNewMapPoints; pinhole
+        keyframes) for pairs of a batch image after undistort_grid() (keyframe 1) and a keyframe the
+        host gives (keyframe 2).  frames: the batch image of each pair (one image may serve several
+        pairs); kf_points: a list (one per pair) of TRIANG_POINT_DTYPE arrays, or (points, offsets)
+        in the C ABI's form; pairs: TRIANG_PAIR_DTYPE array, one row per pair (F12 and the epipole);
+        f_nodes: a list of int32 arrays (the node of each keypoint of keyframe 1, < 0: none) or one
+        2-D array [n_pairs, stride]; f_flags: the same shape in uint8 with TRI_HAS_POINT /
+        TRI_STEREO per keypoint of keyframe 1, None: neither anywhere."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        npairs = len(fr)
+        pts, off, _ = self._map_point_rows(kf_points, TRIANG_POINT_DTYPE, npairs)
+        pr = np.ascontiguousarray(pairs, TRIANG_PAIR_DTYPE).reshape(-1)
+        if len(pr) != npairs:
+            raise ValueError("one F12 and epipole per pair")
+        nodes, _ = self._pad_rows(f_nodes, np.int32, -1)
+        if nodes.shape[0] != npairs:
+            raise ValueError("one row of nodes per pair")
+        flg, fstride = self._pad_rows(f_flags, np.uint8, 0)
+        if flg is not None and flg.shape[0] != npairs:
+            raise ValueError("one row of flags per pair")
+        _check(_lib.orbgpu_search_for_triangulation_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(pts) if npairs else None,
+            _p(off) if npairs else None, _p(pr) if npairs else None, _p(nodes) if npairs else None,
+            nodes.shape[1] if npairs else 0, _p(flg) if flg is not None and npairs else None, fstride,
+            int(only_stereo), int(coarse), int(check_orientation), C.c_void_p(stream) if stream else None))
+
+    def triangulation_matches(self, pair, cap=65536):
+        """(match12 [N1] int32: for each keypoint of keyframe 1 the index, within the pair's keyframe
+        points, left in vMatches12, -1 if none; nmatches; rot_hist [30] int32: the bin sizes before the
+        three-maxima rule) of pair `pair` of the last search_for_triangulation.  vMatchedPairs =
+        [(k, match12[k]) for k in np.flatnonzero(match12 >= 0)]."""
+        return self._download_matches(_lib.orbgpu_download_triangulation_matches, pair, cap)
 
     def reloc_by_projection(self, frames, kf_points, poses, K, kp_block=None, th=10.0, orb_dist=100,
                             check_orientation=True, stream=None):

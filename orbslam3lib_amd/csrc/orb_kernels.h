@@ -558,6 +558,52 @@ struct BowArgs {
 // max_side: the largest keypoint count of a side (<= kBowMaxPoints)
 hipError_t launch_bow_search(const BowArgs& a, int npairs, int max_side, hipStream_t st);
 
+// ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (orb_tri.hip),
+// pinhole keyframes.  Keyframe 1 is a batch image, keyframe 2 the host's points; the grouping fields
+// carry BowArgs' names (orb_bow_group.h reads them from either struct).
+struct TriPoint {  // orbgpu_triang_point (56 B)
+    uint32_t desc[8];
+    float x, y, angle;
+    int32_t octave, node, flags;
+};
+constexpr int kTriHasPoint = 1, kTriStereo = 2;
+struct TriPair {  // orbgpu_triang_pair (44 B)
+    float F12[9], ep[2];
+};
+struct TriArgs {
+    const int32_t* frames;    // [pair] the batch image that is keyframe 1
+    const TriPoint* kf_pts;   // all pairs' keyframe 2 points, pair p = [kf_off[p], kf_off[p + 1])
+    const int32_t* kf_off;    // [pair + 1], kf_off[0] == 0
+    const TriPair* pairs;     // [pair]
+    const int32_t* f_nodes;   // [pair][out_cap] the node of each keypoint of keyframe 1, < 0: none
+    const uint8_t* f_flags;   // [pair][out_cap] kTriHasPoint / kTriStereo of keyframe 1's keypoints, or nullptr
+    const double* epi_th;     // [kMaxLevels] 3.84 * (double)mvLevelSigma2[level] (Pinhole.cpp:123)
+    const float* disc_th;     // [kMaxLevels] 100 * mvScaleFactors[level] (:1037)
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const uint8_t* desc;      // out_desc
+    const float* xy_un;       // [img][out_cap][2] mvKeysUn positions (orbgpu_undistort_grid_batch)
+    int nlevels;
+    int only_stereo, coarse, check_orientation;
+    // k_tri_group -> k_tri_match: each side's keypoints by (node, index) and its node segments
+    int32_t* kf_order;        // [kf point]
+    int32_t* kf_seg_node;     // [kf point]
+    int32_t* kf_seg_start;    // pair p at kf_off[p] + p, one entry more than its points
+    int32_t* f_order;         // [pair][out_cap]
+    int32_t* f_seg_node;      // [pair][out_cap]
+    int32_t* f_seg_start;     // [pair][out_cap + 1]
+    uint8_t* f_desc;          // [pair][out_cap][32] keyframe 1's descriptors in f_order's order
+    uint4* kf_desc;           // [kf point][2] keyframe 2's descriptors in kf_order's order
+    float4* kf_meta;          // [kf point] {x, y, angle, bits of octave << 8 | flags} in kf_order's order
+    int32_t* nseg;            // [pair][2] segments of keyframe 2, of keyframe 1
+    int32_t* match;           // [pair][out_cap] vMatches12
+    uint8_t* match_bin;       // [pair][out_cap] the bin of the event that wrote match
+    int32_t* nmatches;        // [pair]
+    int32_t* rot_hist;        // [pair][kRotBins] bin sizes before the three-maxima rule
+};
+hipError_t launch_tri_search(const TriArgs& a, int npairs, int max_side, hipStream_t st);
+
 // ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist)
 // (orb_reloc.hip).
 struct RelocPoint {  // orbgpu_reloc_point (60 B)

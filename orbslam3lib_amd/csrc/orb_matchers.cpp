@@ -1,8 +1,8 @@
 // orb_matchers.cpp -- the part of the C ABI (include/orbgpu.h) that runs the ORBmatcher searches over
 // the device-resident results of a batch: the local-map search (orb_sbp.hip), the motion-model search
-// (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip) and
-// the relocalisation search (orb_reloc.hip).  Every entry point validates its own arguments and lays
-// out its own buffers; what they share -- the offsets check, the padded row uploads, the common
+// (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip), the
+// triangulation search (orb_tri.hip) and the relocalisation search (orb_reloc.hip).  Every entry
+// point validates its own arguments and lays out its own buffers; what they share -- the offsets check, the padded row uploads, the common
 // argument fields, the launch path and the download -- is written once, below.
 #include <cmath>
 
@@ -524,6 +524,119 @@ int orbgpu_download_bow_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
     return download_matches(c, c->bow_cover, pair, "bad pair", c->bowmatch.as<int32_t>(), c->bownm.as<int32_t>(),
                             row_cap(c, false), match, cap, n_kp, nmatches, rot_hist);
+}
+
+// ---- ORBmatcher::SearchForTriangulation(pKF1, pKF2, ...) on pinhole keyframes (orb_tri.hip) --------
+static_assert(sizeof(orbgpu_triang_point) == 56 && sizeof(TriPoint) == 56, "orbgpu_triang_point is 56 bytes");
+static_assert(sizeof(orbgpu_triang_pair) == 44 && sizeof(TriPair) == 44, "orbgpu_triang_pair is 44 bytes");
+static_assert(ORBGPU_TRI_HAS_POINT == kTriHasPoint && ORBGPU_TRI_STEREO == kTriStereo, "the header states the flag bits");
+
+int orbgpu_search_for_triangulation_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames,
+                                          const orbgpu_triang_point* kf_pts, const int32_t* kf_offsets,
+                                          const orbgpu_triang_pair* pairs, const int32_t* f_nodes, int node_stride,
+                                          const uint8_t* f_flags, int flag_stride, int only_stereo, int coarse,
+                                          int check_orientation, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !pairs || !f_nodes))
+        return fail(ORBGPU_ERR_INVALID, "null array");
+    for (int p = 0; p < n_pairs; ++p)
+        if (frames[p] < 0 || frames[p] >= c->grid_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
+    int max_kf, total;
+    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", &max_kf, &total)) return e;
+    if (n_pairs > 0 && (node_stride < 0 || (f_flags && flag_stride < 0)))
+        return fail(ORBGPU_ERR_INVALID, "negative stride");
+    if (n_pairs == 0) {
+        c->tri_cover.image.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nkf = (size_t)total;
+    const int max_side = std::max((int)cap, max_kf);
+    if (max_side > kBowMaxPoints)
+        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    for (size_t i = 0; i < nkf; ++i)  // the level tables are indexed with it
+        if (kf_pts[kf_offsets[0] + i].octave < 0 || kf_pts[kf_offsets[0] + i].octave >= c->prm.nlevels)
+            return fail(ORBGPU_ERR_INVALID, "octave of a keyframe point outside [0, nlevels)");
+    // one row of nodes (and of flags) per pair: it must cover keyframe 1's keypoints
+    if (int e = rows_cover_counts(c, c->grid_images, frames, 1, n_pairs, f_flags ? std::min(node_stride, flag_stride) : node_stride,
+                                  "node_stride or flag_stride below the frame's keypoint count"))
+        return e;
+    // triin: frames [np], offsets [np + 1], the pairs, then (8-byte aligned) the two level tables
+    const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
+    const size_t pairs_at = head.size() * 4, tab_at = (pairs_at + np * sizeof(TriPair) + 7) & ~(size_t)7;
+    std::vector<uint8_t> in(tab_at + kMaxLevels * 12, 0);
+    std::memcpy(in.data(), head.data(), pairs_at);
+    std::memcpy(in.data() + pairs_at, pairs, np * sizeof(TriPair));
+    for (int l = 0; l < c->prm.nlevels; ++l) {
+        const double epi = 3.84 * (double)c->tab.sigma2[l];  // Pinhole.cpp:123: a double product
+        const float disc = (float)100 * c->tab.scale[l];     // :1037: int * float
+        std::memcpy(in.data() + tab_at + 8 * (size_t)l, &epi, 8);
+        std::memcpy(in.data() + tab_at + 8 * (size_t)kMaxLevels + 4 * (size_t)l, &disc, 4);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // trigrp: the BoW search's layout (kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order,
+    // f_seg_node [np * cap each], f_seg_start [np * (cap + 1)], nseg [2 np]); tripack: keyframe 2's packed
+    // rows, 32 B of descriptor and 16 B of {x, y, angle, octave and flags} per point
+    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
+    if (c->triin.ensure(in.size() + 256) || c->trikf.ensure(nkf * sizeof(TriPoint) + 256) ||
+        c->trifn.ensure(np * cap * 4 + 256) || (f_flags && c->triflag.ensure(np * cap + 256)) ||
+        c->trigrp.ensure(grp_words * 4 + 256) || c->tridesc.ensure(np * cap * 32 + 256) ||
+        c->tripack.ensure(nkf * 48 + 256) || c->trimatch.ensure(np * cap * 5 + 256) ||
+        c->trinm.ensure(np * (1 + kRotBins) * 4 + 256))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (triangulation search)");
+    TriArgs a{};
+    a.frames = c->triin.as<int32_t>();
+    a.kf_off = a.frames + np;
+    a.pairs = reinterpret_cast<const TriPair*>(c->triin.as<uint8_t>() + pairs_at);
+    a.epi_th = reinterpret_cast<const double*>(c->triin.as<uint8_t>() + tab_at);
+    a.disc_th = reinterpret_cast<const float*>(a.epi_th + kMaxLevels);
+    a.kf_pts = c->trikf.as<TriPoint>();
+    a.f_nodes = c->trifn.as<int32_t>();
+    a.f_flags = f_flags ? c->triflag.as<uint8_t>() : nullptr;
+    bind_frame(a, c);
+    a.xy_un = c->gxy.as<float>();
+    a.nlevels = c->prm.nlevels;
+    a.only_stereo = only_stereo != 0;
+    a.coarse = coarse != 0;
+    a.check_orientation = check_orientation != 0;
+    a.kf_order = c->trigrp.as<int32_t>();
+    a.kf_seg_node = a.kf_order + nkf;
+    a.kf_seg_start = a.kf_seg_node + nkf;
+    a.f_order = a.kf_seg_start + nkf + np;
+    a.f_seg_node = a.f_order + np * cap;
+    a.f_seg_start = a.f_seg_node + np * cap;
+    a.nseg = a.f_seg_start + np * (cap + 1);
+    a.f_desc = c->tridesc.as<uint8_t>();
+    a.kf_desc = c->tripack.as<uint4>();
+    a.kf_meta = reinterpret_cast<float4*>(a.kf_desc + 2 * nkf);
+    a.match = c->trimatch.as<int32_t>();
+    a.match_bin = reinterpret_cast<uint8_t*>(a.match + np * cap);
+    a.nmatches = c->trinm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_pairs;
+    const int r = run_search(
+        c, stream,
+        [&](hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(c->triin.p, in.data(), in.size(), hipMemcpyHostToDevice, s));
+            if (nkf)
+                HIP_TRY(hipMemcpyAsync(c->trikf.p, kf_pts + kf_offsets[0], nkf * sizeof(TriPoint), hipMemcpyHostToDevice, s));
+            if (f_flags)
+                if (int e = upload_rows(c->triflag.p, cap, f_flags, (size_t)flag_stride, std::min((size_t)flag_stride, cap), np, 0, s))
+                    return e;
+            return upload_rows(c->trifn.p, cap * 4, f_nodes, (size_t)node_stride * 4,
+                               std::min((size_t)node_stride, cap) * 4, np, -1, s);
+        },
+        [&](hipStream_t s) { return launch_tri_search(a, n_pairs, max_side, s); });
+    if (r) return r;
+    set_cover(c->tri_cover, np, frames, 1, false);
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_triangulation_matches(orbgpu_ctx* c, int pair, int32_t* match12, int cap, int* n1, int* nmatches,
+                                          int32_t rot_hist[30]) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    return download_matches(c, c->tri_cover, pair, "bad pair", c->trimatch.as<int32_t>(), c->trinm.as<int32_t>(),
+                            row_cap(c, false), match12, cap, n1, nmatches, rot_hist);
 }
 
 // ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (orb_reloc.hip) ----
