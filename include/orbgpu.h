@@ -524,7 +524,7 @@ int orbgpu_download_bow_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int c
  * entries, k ascending (:1142-1150).  Errors as for orbgpu_download_bow_matches.
  * Not built: the two-camera SearchForTriangulation (mpCamera2 set: the Tll / Tlr / Trl / Trr
  * selection :1043-1077 and KannalaBrandt8::epipolarConstrain, which triangulates), SearchByBoW(KeyFrame*,
- * KeyFrame*), Fuse and the Sim3 searches (SearchBySim3, the Sim3 SearchByProjection overloads). */
+ * KeyFrame*) and the Sim3 searches (SearchBySim3, the Sim3 SearchByProjection overloads). */
 typedef struct {
     uint8_t desc[32];  /* pKF2->mDescriptors.row(i) */
     float x, y;        /* pKF2->mvKeysUn[i].pt */
@@ -618,6 +618,101 @@ int orbgpu_download_reloc_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int
  * them: its own logf need not equal the host's near a step.  ORBGPU_ERR_INVALID: scale_factor not
  * above 1, nlevels outside [1, 16], a null table with nlevels > 1. */
 int orbgpu_predict_scale_table(float scale_factor, int nlevels, float* thresholds);
+
+/* ---- ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th, bRight = false) ----
+ * The map-point fusion LocalMapping::SearchInNeighbors (LocalMapping.cc:726-815) runs right after
+ * CreateNewMapPoints -- once per neighbour keyframe with the current keyframe's points, once on the
+ * current keyframe with every neighbour's points -- cpp/src/ORBmatcher.cc:1155-1345, and the Sim3
+ * overload LoopClosing::SearchAndFuse calls (:1347-1462, sim3 != 0: the same search without the
+ * chi-square gate), with KeyFrame::GetFeaturesInArea / IsInImage (KeyFrame.cc:706-755) and
+ * MapPoint::PredictScale (MapPoint.cc:516-531), on pinhole keyframes (NLeft == -1: mvKeysUn, mvuRight).
+ * Pair p fuses list lists[p] -- the points pts[list_offsets[l], list_offsets[l + 1]) -- into batch image
+ * frames[p], inside the range of the last orbgpu_undistort_grid_batch, under pose p: Rcw, tcw, Ow of
+ * pKF->GetPose() / GetCameraCenter(); for the Sim3 overload Scw.rotationMatrix(), Scw.translation() /
+ * Scw.scale() and the inverse's translation (:1356-1357).  Several pairs may name one list
+ * (SearchInNeighbors' forward leg: one upload of the current keyframe's points for all neighbours)
+ * and several pairs one frame.  All arithmetic is IEEE single, evaluated in the reference's order.
+ * The points do not see each other.  Each point i gets the decision code of the reference's count_*
+ * debug counters (:1183):
+ *   1. ORBGPU_FUSE_SKIPPED: the point lacks ORBGPU_FP_VALID (!pMP, isBad(), :1188-1198) or skip[p][i]
+ *      is non-zero (IsInKeyFrame(pKF) :1199, spAlreadyFound.count :1372).
+ *   2. ORBGPU_FUSE_NEG_DEPTH: p3Dc = Tcw * X, row by row as ((R0 x + R1 y) + R2 z) + t; zc < 0.0f
+ *      (:1209).  invz = 1 / zc.
+ *   3. ORBGPU_FUSE_NOT_IN_IMAGE: u = fx * xc / zc + cx, v = fy * yc / zc + cy (Pinhole.cpp:40-41) fail
+ *      KeyFrame::IsInImage (KeyFrame.cc:752-755), u >= mnMinX && u < mnMaxX && v >= mnMinY && v < mnMaxY:
+ *      half-open, unlike the relocalisation search's closed test.  A NaN or infinite projection fails
+ *      it, as in the reference (zc == +-0 ends here).
+ *   4. ORBGPU_FUSE_DISTANCE: ur = u - bf * invz; PO = X - Ow; dist3D = sqrtf((PO.x * PO.x + PO.y * PO.y)
+ *      + PO.z * PO.z); dist3D < 0.8f * min_distance || dist3D > 1.2f * max_distance (:1234,
+ *      MapPoint.cc:504-514).  Deviation: a dist3D or max_distance / dist3D that is not finite also
+ *      gets this code (the reference would go on into PredictScale with it).
+ *   5. ORBGPU_FUSE_NORMAL: (PO.x * n.x + PO.y * n.y) + PO.z * n.z < 0.5 * dist3D (:1242), compared in
+ *      double: 0.5 is a double literal.
+ *   6. nPredictedLevel = MapPoint::PredictScale(dist3D, pKF) as for orbgpu_reloc_by_projection_batch
+ *      (orbgpu_predict_scale_table); radius = th * mvScaleFactors[level] (:1248-1251).
+ *   7. ORBGPU_FUSE_EMPTY_WINDOW: KeyFrame::GetFeaturesInArea(u, v, radius) -- the cells of
+ *      Frame::GetFeaturesInArea, columns, then rows, then the index within the cell, fabs(dx) < radius
+ *      && fabs(dy) < radius, no level filter -- is empty (:1255), before any per-candidate filter.
+ *   8. over that list in order: an octave outside [level - 1, level] is passed over (:1276); unless
+ *      sim3, the chi-square gate (:1279-1303): with use_uright and mvuRight[k] >= 0, e2 = (ex * ex + ey *
+ *      ey) + er * er (er = ur - mvuRight[k]) and the keypoint is passed over when (double)(e2 *
+ *      mvInvLevelSigma2[octave]) > 7.8; otherwise e2 = ex * ex + ey * ey and the limit is 5.99.  The
+ *      product is a float, the literals are doubles; a NaN product passes, as in the reference.  The
+ *      best is the first lowest Hamming distance, strict < from 256.
+ *   9. ORBGPU_FUSE_FUSED when bestDist <= 50 (TH_LOW, :1319), else ORBGPU_FUSE_ABOVE_TH_LOW
+ *      (count_thcheck), also when every candidate was passed over.
+ * Parity with the reference is unpinned, as for the other matcher functions: the yardstick is the
+ * Python restatement in tests/test_fuse.py.
+ * skip ([n_pairs][skip_stride] u8, host; NULL: none): [p][i] != 0 where point i of the pair's list is
+ * already in keyframe p.  use_uright: the mvuRight row orbgpu_search_by_projection_batch reads for
+ * that image, under that call's conditions: every frames[p] must then be the left image (2j) of a pair
+ * j of the last orbgpu_stereo_matches_batch; with 0 every keypoint takes the monocular gate.  sim3 !=
+ * 0 drops the gate and ignores bf and use_uright.  K = {fx, fy, cx, cy}; bf = pKF->mbf.  Host arrays
+ * are pageable and may be reused when the call returns.
+ * ORBGPU_ERR_INVALID: null context, n_pairs < 0 or above the context's image capacity, null arrays
+ * with work to do, a frame outside the gridded range, lists[p] outside [0, n_lists), list_offsets not
+ * ascending from a value >= 0, skip_stride below a named list's length, th or (unless sim3) bf
+ * negative or not finite, the use_uright conditions not met.  ORBGPU_ERR_CAPACITY: a list above
+ * ORBGPU_FUSE_MAX_POINTS.  n_pairs == 0 succeeds and leaves no pair to download.  Every status is
+ * decided before any launch.
+ * orbgpu_download_fuse_matches, per point of the pair's list: code[i]; best_dist[i] = the lowest
+ * distance that survived the filters, 256 when none did or the point never reached them (the Sim3
+ * overload starts from INT_MAX, so a 256-bit complement can become its bestIdx: it can never fuse,
+ * and 256 stands for it); best_idx[i] = bestIdx when fused, else -1.  Per keypoint k of the frame:
+ * first[k] = the lowest i that fused onto k, -1 if none.  *nfused = the reference's return value.
+ * The host replays :1321-1337 / :1446-1456 from them: for i ascending with best_idx[i] = k >= 0, the
+ * point met in pKF->GetMapPoint(k) is the keyframe's own if it holds one, else none when first[k] == i
+ * (AddObservation / AddMapPoint), else point first[k] of the list.  *n_points = the list's length,
+ * *n_kp = N; ORBGPU_ERR_CAPACITY when cap_points < *n_points or cap_kp < *n_kp (both counts are
+ * written first); otherwise errors as for orbgpu_download_bow_matches.
+ * Not built: the two-camera form (bRight, NLeft != -1: mvKeys / mvKeysRight, GetRightPose),
+ * SearchBySim3 and the Sim3 SearchByProjection overloads, and the host-side Replace / AddObservation
+ * bookkeeping. */
+typedef struct {
+    float pos[3];        /* pMP->GetWorldPos() */
+    float normal[3];     /* pMP->GetNormal() */
+    float min_distance;  /* pMP->mfMinDistance (the 0.8f factor is applied here) */
+    float max_distance;  /* pMP->mfMaxDistance (1.2f for the gate, raw for PredictScale) */
+    int32_t flags;       /* ORBGPU_FP_VALID: pMP && !pMP->isBad() */
+    uint8_t desc[32];    /* pMP->GetDescriptor() */
+} orbgpu_fuse_point;     /* 68 bytes */
+#define ORBGPU_FP_VALID 1
+#define ORBGPU_FUSE_MAX_POINTS 65536
+#define ORBGPU_FUSE_SKIPPED 1
+#define ORBGPU_FUSE_NEG_DEPTH 2
+#define ORBGPU_FUSE_NOT_IN_IMAGE 3
+#define ORBGPU_FUSE_DISTANCE 4
+#define ORBGPU_FUSE_NORMAL 5
+#define ORBGPU_FUSE_EMPTY_WINDOW 6
+#define ORBGPU_FUSE_ABOVE_TH_LOW 7
+#define ORBGPU_FUSE_FUSED 8
+
+int orbgpu_fuse_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames, const int32_t* lists, int n_lists,
+                      const orbgpu_fuse_point* pts, const int32_t* list_offsets, const orbgpu_reloc_pose* poses,
+                      const float K[4], const uint8_t* skip, int skip_stride, float th, float bf, int use_uright,
+                      int sim3, void* stream);
+int orbgpu_download_fuse_matches(orbgpu_ctx* ctx, int pair, int32_t* best_idx, int32_t* best_dist, uint8_t* code,
+                                 int cap_points, int32_t* first, int cap_kp, int* n_points, int* n_kp, int* nfused);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

@@ -20,7 +20,7 @@ import numpy as np
 
 __all__ = ["ORBextractor", "ORBmatcher", "BFMatcher", "BatchExtractor", "KEYPOINT_DTYPE", "MAP_POINT_DTYPE",
            "LAST_POINT_DTYPE", "TRACK_POSE_DTYPE", "RELOC_POINT_DTYPE", "RELOC_POSE_DTYPE", "TRIANG_POINT_DTYPE",
-           "TRIANG_PAIR_DTYPE", "predict_scale_table",
+           "TRIANG_PAIR_DTYPE", "FUSE_POINT_DTYPE", "predict_scale_table",
            "OrbGpuError", "load_library", "LIB_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -57,6 +57,14 @@ RELOC_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("min_dist
                               ("max_distance", "<f4"), ("flags", "<i4"), ("desc", "u1", (32,))])
 RELOC_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,))])
 RP_VALID = 1  # ORBGPU_RP_VALID
+# orbgpu_fuse_point (68 B): a map point for fuse; the poses are RELOC_POSE_DTYPE rows
+FUSE_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
+                             ("max_distance", "<f4"), ("flags", "<i4"), ("desc", "u1", (32,))])
+FP_VALID = 1  # ORBGPU_FP_VALID
+FUSE_MAX_POINTS = 65536  # ORBGPU_FUSE_MAX_POINTS
+# ORBGPU_FUSE_*: the decision a point ended with (the reference's count_* counters, ORBmatcher.cc:1183)
+(FUSE_SKIPPED, FUSE_NEG_DEPTH, FUSE_NOT_IN_IMAGE, FUSE_DISTANCE, FUSE_NORMAL, FUSE_EMPTY_WINDOW, FUSE_ABOVE_TH_LOW,
+ FUSE_FUSED) = range(1, 9)
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -84,6 +92,7 @@ EXPORTED = [
     "orbgpu_download_initialization_matches", "orbgpu_search_by_bow_batch", "orbgpu_download_bow_matches",
     "orbgpu_reloc_by_projection_batch", "orbgpu_download_reloc_matches", "orbgpu_predict_scale_table",
     "orbgpu_search_for_triangulation_batch", "orbgpu_download_triangulation_matches",
+    "orbgpu_fuse_batch", "orbgpu_download_fuse_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -935,6 +944,53 @@ class BatchExtractor:
         int32: the bin sizes before the three-maxima rule) of pair `pair` of the last
         reloc_by_projection."""
         return self._download_matches(_lib.orbgpu_download_reloc_matches, pair, cap)
+
+    def fuse(self, frames, lists, point_lists, poses, K, skip=None, th=3.0, bf=0.0, use_uright=False, sim3=False,
+             stream=None):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:1155-1345, LocalMapping::SearchInNeighbors;
+        pinhole keyframes) and, with sim3, the Sim3 overload (:1347-1462, LoopClosing::SearchAndFuse) for
+        pairs of a list of map points and a batch image after undistort_grid().  frames: the batch image
+        of each pair; lists: the list each pair fuses (several pairs may name one list, or one frame);
+        point_lists: a list of FUSE_POINT_DTYPE arrays, or (points, offsets) in the C ABI's form;
+        poses: RELOC_POSE_DTYPE array, one row per pair (Rcw, tcw, Ow); K = (fx, fy, cx, cy); skip:
+        optional list (one per pair) of u8 arrays over the pair's list, or one 2-D array (non-zero = the
+        point is already in that keyframe); bf = pKF->mbf; use_uright: the keypoints with a right
+        coordinate (after stereo_matches; every frame a left image) take the stereo chi-square gate."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        ls = np.ascontiguousarray(lists, np.int32).reshape(-1)
+        npairs = len(fr)
+        if len(ls) != npairs:
+            raise ValueError("one list index per pair")
+        if isinstance(point_lists, tuple):
+            pts, off, nl = self._map_point_rows(point_lists, FUSE_POINT_DTYPE, len(point_lists[1]) - 1)
+        else:
+            pts, off, nl = self._map_point_rows(point_lists, FUSE_POINT_DTYPE)
+        ps = np.ascontiguousarray(poses, RELOC_POSE_DTYPE).reshape(-1)
+        if len(ps) != npairs:
+            raise ValueError("one pose per pair")
+        Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
+        sk, stride = self._pad_rows(skip, np.uint8, 0)
+        if sk is not None and sk.shape[0] != npairs:
+            raise ValueError("one row of skip flags per pair")
+        _check(_lib.orbgpu_fuse_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(ls) if npairs else None, nl,
+            _p(pts) if len(pts) else None, _p(off), _p(ps) if npairs else None, _p(Kf),
+            _p(sk) if sk is not None and npairs else None, stride, C.c_float(th), C.c_float(bf), int(use_uright),
+            int(sim3), C.c_void_p(stream) if stream else None))
+
+    def fuse_matches(self, pair, cap_points=FUSE_MAX_POINTS, cap_kp=65536):
+        """(best_idx [n] int32: the keypoint point i fused onto, else -1; best_dist [n] int32: the lowest
+        distance that survived the filters, 256 if none; code [n] uint8: FUSE_*; first [N] int32: for
+        each keypoint of the frame the lowest point that fused onto it, -1 if none; nfused) of pair
+        `pair` of the last fuse."""
+        bi = np.zeros(cap_points, np.int32)
+        bd = np.zeros(cap_points, np.int32)
+        cd = np.zeros(cap_points, np.uint8)
+        first = np.zeros(cap_kp, np.int32)
+        n, nk, nf = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_fuse_matches(self.ctx.handle, pair, _p(bi), _p(bd), _p(cd), cap_points, _p(first),
+                                                 cap_kp, C.byref(n), C.byref(nk), C.byref(nf)))
+        return bi[:n.value], bd[:n.value], cd[:n.value], first[:nk.value], nf.value
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

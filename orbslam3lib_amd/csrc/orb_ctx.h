@@ -138,10 +138,12 @@ struct orbgpu_ctx {
         inicand{bufs}, inil0{bufs}, inimatch{bufs}, inipout{bufs}, ininm{bufs}, bowin{bufs}, bowkf{bufs}, bowfn{bufs},
         bowgrp{bufs}, bowdesc{bufs}, bowmatch{bufs}, bownm{bufs}, relin{bufs}, relpt{bufs}, relpose{bufs},
         relcand{bufs}, relblk{bufs}, relmatch{bufs}, relnm{bufs}, triin{bufs}, trikf{bufs}, trifn{bufs}, triflag{bufs},
-        trigrp{bufs}, tridesc{bufs}, tripack{bufs}, trimatch{bufs}, trinm{bufs};
+        trigrp{bufs}, tridesc{bufs}, tripack{bufs}, trimatch{bufs}, trinm{bufs}, fusein{bufs}, fusept{bufs}, fusepose{bufs},
+        fuseskip{bufs}, fuseout{bufs}, fusefirst{bufs}, fusenf{bufs};
     float grid_bounds[4] = {0, 0, 0, 0}, grid_inv[2] = {0, 0};  // of the last undistort_grid
     // coverage of the last call of each ORBmatcher search (orb_matchers.cpp; init_cover: F1 of each pair)
-    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover, tri_cover;
+    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover, tri_cover, fuse_cover;
+    std::vector<int32_t> fuse_off;  // the last orbgpu_fuse_batch: pair p's point rows are [fuse_off[p], fuse_off[p + 1])
     int soa_images = 0, soa_pairs = 0;  // coverage of the last orbgpu_pack_soa
     int grid_images = 0;   // images of the last orbgpu_undistort_grid_batch
     int stereo_pairs = 0;  // pairs of the last orbgpu_stereo_matches_batch

@@ -649,6 +649,50 @@ struct RelocArgs {
 size_t reloc_resolve_lds_bytes(int out_cap);
 hipError_t launch_reloc(const RelocArgs& a, int npairs, int max_pts, hipStream_t st);
 
+// ORBmatcher::Fuse(pKF, vpMapPoints, th) and its Sim3 overload on pinhole keyframes (orb_fuse.hip).
+struct FusePoint {  // orbgpu_fuse_point (68 B)
+    float pos[3], normal[3], min_distance, max_distance;
+    int32_t flags;
+    uint8_t desc[32];
+};
+constexpr int kFpValid = 1;
+constexpr int kFuseMaxPoints = 65536;  // ORBGPU_FUSE_MAX_POINTS
+enum FuseCode : uint8_t {  // ORBGPU_FUSE_*
+    kFuseSkipped = 1, kFuseNegDepth, kFuseNotInImage, kFuseDistance, kFuseNormal, kFuseEmptyWindow, kFuseAboveThLow,
+    kFuseFused
+};
+struct FuseArgs {
+    const int32_t* frames;    // [pair] the batch image that is pKF
+    const int32_t* lists;     // [pair] the list the pair fuses
+    const int32_t* out_off;   // [pair + 1] the pair's rows of best_idx / best_dist / code
+    const int32_t* list_off;  // [list + 1], list_off[0] == 0
+    const FusePoint* pts;     // all lists' points
+    const RelocPose* poses;   // [pair]
+    const uint8_t* skip;      // [pair][skip_stride] non-zero: the point is skipped for this pair; or nullptr
+    int skip_stride;
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const float* xy_un;       // grid buffers (orbgpu_undistort_grid_batch)
+    const int32_t* cell_start;
+    const int32_t* cell_idx;
+    const uint8_t* desc;      // out_desc
+    const float* uright;      // mvuRight [stereo pair][out_cap] (pair = image / 2), or nullptr
+    float bounds[4], grid_inv[2];
+    float scale[kMaxLevels];
+    float inv_sigma2[kMaxLevels];  // mvInvLevelSigma2
+    float level_step[kMaxLevels];  // predict_scale_table, as in RelocArgs
+    int nlevels;
+    float K[4], th, bf;
+    int sim3;                 // the Sim3 overload: no chi-square gate
+    int32_t* best_idx;        // [point row]
+    int32_t* best_dist;       // [point row]
+    uint8_t* code;            // [point row]
+    uint32_t* first;          // [pair][out_cap] lowest point that fused onto the keypoint; 0xFFFFFFFF (-1): none
+    int32_t* nfused;          // [pair]
+};
+hipError_t launch_fuse(const FuseArgs& a, int npairs, int max_pts, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

@@ -1,7 +1,8 @@
 // orb_matchers.cpp -- the part of the C ABI (include/orbgpu.h) that runs the ORBmatcher searches over
 // the device-resident results of a batch: the local-map search (orb_sbp.hip), the motion-model search
 // (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip), the
-// triangulation search (orb_tri.hip) and the relocalisation search (orb_reloc.hip).  Every entry
+// triangulation search (orb_tri.hip), the relocalisation search (orb_reloc.hip) and the map-point fusion
+// (orb_fuse.hip).  Every entry
 // point validates its own arguments and lays out its own buffers; what they share -- the offsets check, the padded row uploads, the common
 // argument fields, the launch path and the download -- is written once, below.
 #include <cmath>
@@ -724,6 +725,125 @@ int orbgpu_download_reloc_matches(orbgpu_ctx* c, int pair, int32_t* match, int c
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
     return download_matches(c, c->reloc_cover, pair, "bad pair", c->relmatch.as<int32_t>(), c->relnm.as<int32_t>(),
                             row_cap(c, false), match, cap, n_kp, nmatches, rot_hist);
+}
+
+// ---- ORBmatcher::Fuse(pKF, vpMapPoints, th) and its Sim3 overload on pinhole keyframes (orb_fuse.hip) ----
+static_assert(sizeof(orbgpu_fuse_point) == 68 && sizeof(FusePoint) == 68, "orbgpu_fuse_point is 68 bytes");
+static_assert(ORBGPU_FP_VALID == kFpValid && ORBGPU_FUSE_MAX_POINTS == kFuseMaxPoints, "the header states the kernel's constants");
+static_assert(ORBGPU_FUSE_SKIPPED == kFuseSkipped && ORBGPU_FUSE_NEG_DEPTH == kFuseNegDepth &&
+                  ORBGPU_FUSE_NOT_IN_IMAGE == kFuseNotInImage && ORBGPU_FUSE_DISTANCE == kFuseDistance &&
+                  ORBGPU_FUSE_NORMAL == kFuseNormal && ORBGPU_FUSE_EMPTY_WINDOW == kFuseEmptyWindow &&
+                  ORBGPU_FUSE_ABOVE_TH_LOW == kFuseAboveThLow && ORBGPU_FUSE_FUSED == kFuseFused,
+              "the header states the decision codes");
+
+int orbgpu_fuse_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const int32_t* lists, int n_lists,
+                      const orbgpu_fuse_point* pts, const int32_t* list_offsets, const orbgpu_reloc_pose* poses,
+                      const float K[4], const uint8_t* skip, int skip_stride, float th, float bf, int use_uright,
+                      int sim3, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ORBGPU_ERR_INVALID, "th negative or not finite");
+    const bool gate = sim3 == 0, stereo = gate && use_uright != 0;
+    if (gate && (!(bf >= 0.0f) || !std::isfinite(bf))) return fail(ORBGPU_ERR_INVALID, "bf negative or not finite");
+    if (n_pairs > 0 && (!frames || !lists || !list_offsets || !poses || !K)) return fail(ORBGPU_ERR_INVALID, "null array");
+    if (n_pairs > 0 && n_lists < 1) return fail(ORBGPU_ERR_INVALID, "no lists");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (frames[p] < 0 || frames[p] >= c->grid_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
+        if (lists[p] < 0 || lists[p] >= n_lists) return fail(ORBGPU_ERR_INVALID, "list outside [0, n_lists)");
+        if (stereo && ((frames[p] & 1) || frames[p] / 2 >= c->stereo_pairs))
+            return fail(ORBGPU_ERR_INVALID, "mvuRight needs the left image of a pair of the last stereo_matches_batch");
+    }
+    int max_list = 0, total_pts = 0;
+    if (n_pairs > 0)
+        if (int e = check_offsets(list_offsets, n_lists, true, "list_offsets", &max_list, &total_pts)) return e;
+    if (total_pts > 0 && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
+    int max_pts = 0;  // over the lists the pairs name
+    for (int p = 0; p < n_pairs; ++p) max_pts = std::max(max_pts, list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
+    if (n_pairs > 0 && skip && skip_stride < max_pts) return fail(ORBGPU_ERR_INVALID, "skip_stride below a list's length");
+    if (max_list > kFuseMaxPoints) return fail(ORBGPU_ERR_CAPACITY, "a list holds more than ORBGPU_FUSE_MAX_POINTS points");
+    if ((long long)n_pairs * max_pts > INT32_MAX) return fail(ORBGPU_ERR_CAPACITY, "more point rows than an int32 counts");
+    if (n_pairs == 0) {
+        c->fuse_cover.image.clear();
+        c->fuse_off.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nl = (size_t)n_lists, total = (size_t)total_pts;
+    // fusein: frames [np], lists [np], the pairs' output rows [np + 1], the list offsets rebased to 0 [nl + 1]
+    std::vector<int32_t> head(3 * np + 1 + nl + 1);
+    std::copy(frames, frames + np, head.begin());
+    std::copy(lists, lists + np, head.begin() + np);
+    head[2 * np] = 0;
+    for (size_t p = 0; p < np; ++p)
+        head[2 * np + p + 1] = head[2 * np + p] + (list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
+    for (size_t l = 0; l <= nl; ++l) head[3 * np + 1 + l] = list_offsets[l] - list_offsets[0];
+    const size_t rows = (size_t)head[3 * np];  // at most max_images * ORBGPU_FUSE_MAX_POINTS
+    const size_t skip_pitch = (size_t)std::max(max_pts, 1);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->fusein.ensure(head.size() * 4 + 256) || c->fusept.ensure(total * sizeof(FusePoint) + 256) ||
+        c->fusepose.ensure(np * sizeof(RelocPose) + 256) || (skip && c->fuseskip.ensure(np * skip_pitch + 256)) ||
+        c->fuseout.ensure(rows * 9 + 256) || c->fusefirst.ensure(np * cap * 4 + 256) || c->fusenf.ensure(np * 4 + 256))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (fuse)");
+    FuseArgs a{};
+    a.frames = c->fusein.as<int32_t>();
+    a.lists = a.frames + np;
+    a.out_off = a.lists + np;
+    a.list_off = a.out_off + np + 1;
+    a.pts = c->fusept.as<FusePoint>();
+    a.poses = c->fusepose.as<RelocPose>();
+    a.skip = skip ? c->fuseskip.as<uint8_t>() : nullptr;
+    a.skip_stride = (int)skip_pitch;
+    bind_frame(a, c);
+    bind_grid(a, c);
+    bind_scale(a, c);
+    for (int l = 0; l < kMaxLevels; ++l) a.inv_sigma2[l] = l < c->prm.nlevels ? c->tab.inv_sigma2[l] : 1.0f;
+    a.uright = stereo ? c->stur.as<float>() : nullptr;
+    predict_scale_table(c->prm.scale_factor, c->prm.nlevels, a.level_step);  // MapPoint.cc:516-531
+    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
+    a.th = th;
+    a.bf = gate ? bf : 0.0f;
+    a.sim3 = !gate;
+    a.best_idx = c->fuseout.as<int32_t>();
+    a.best_dist = a.best_idx + rows;
+    a.code = reinterpret_cast<uint8_t*>(a.best_dist + rows);
+    a.first = c->fusefirst.as<uint32_t>();
+    a.nfused = c->fusenf.as<int32_t>();
+    const int r = run_search(
+        c, stream,
+        [&](hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(c->fusein.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
+            if (total)
+                HIP_TRY(hipMemcpyAsync(c->fusept.p, pts + list_offsets[0], total * sizeof(FusePoint), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(c->fusepose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(c->fusefirst.p, 0xFF, np * cap * 4, s));  // -1: no point fused onto the keypoint
+            HIP_TRY(hipMemsetAsync(c->fusenf.p, 0, np * 4, s));
+            if (skip) return upload_rows(c->fuseskip.p, skip_pitch, skip, (size_t)skip_stride, (size_t)max_pts, np, 0, s);
+            return 0;
+        },
+        [&](hipStream_t s) { return launch_fuse(a, n_pairs, max_pts, s); });
+    if (r) return r;
+    set_cover(c->fuse_cover, np, frames, 1, false);
+    c->fuse_off.assign(head.begin() + 2 * np, head.begin() + 3 * np + 1);
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_fuse_matches(orbgpu_ctx* c, int pair, int32_t* best_idx, int32_t* best_dist, uint8_t* code,
+                                 int cap_points, int32_t* first, int cap_kp, int* n_points, int* n_kp, int* nfused) {
+    if (!c || pair < 0 || (size_t)pair >= c->fuse_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    const size_t rows = (size_t)c->fuse_off.back(), row0 = (size_t)c->fuse_off[(size_t)pair];
+    const int n = c->fuse_off[(size_t)pair + 1] - c->fuse_off[(size_t)pair];
+    if (n_points) *n_points = n;
+    // the keypoint side first: both counts are out before either capacity is judged
+    const int r = download_matches(c, c->fuse_cover, pair, "bad pair", c->fusefirst.as<int32_t>(), c->fusenf.as<int32_t>(),
+                                   row_cap(c, false), first, cap_kp, n_kp, nfused, nullptr);
+    if (r && r != ORBGPU_ERR_CAPACITY) return r;
+    if (n > cap_points) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small (points)");
+    if (r) return r;
+    const int32_t* didx = c->fuseout.as<int32_t>();
+    if (best_idx && n) D2H(best_idx, didx + row0, 4 * (size_t)n);
+    if (best_dist && n) D2H(best_dist, didx + rows + row0, 4 * (size_t)n);
+    if (code && n) D2H(code, reinterpret_cast<const uint8_t*>(didx + 2 * rows) + row0, (size_t)n);
+    return ORBGPU_OK;
 }
 
 }  // extern "C"

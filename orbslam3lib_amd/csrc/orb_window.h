@@ -2,7 +2,8 @@
 // descriptors, grid and mvuRight live in HBM, shared by the two projection searches
 // (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search) and, with
 // ComputeThreeMaxima, by the initialisation search (orb_init.hip); the relocalisation and
-// bag-of-words searches (orb_reloc.hip, orb_bow.hip) share its candidate and rotation-bin helpers.
+// bag-of-words searches (orb_reloc.hip, orb_bow.hip) share its candidate and rotation-bin helpers,
+// and the fusion (orb_fuse.hip) walks KeyFrame::GetFeaturesInArea, the same cells, by a group of lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -127,6 +128,57 @@ __device__ inline int walk_window_wave(const Args& a, const FrameView& F, float 
     }
     *best_idx = idx;
     return idx >= 0 ? (int)(key >> 16) : 256;
+}
+
+// KeyFrame::GetFeaturesInArea(x, y, rs) (KeyFrame.cc:706-750: the cells and the order of
+// Frame::GetFeaturesInArea, no level filter) by a group of G adjacent lanes for one window (every
+// lane of the group passes the same arguments, sub = its place in the group): lane sub takes grid
+// columns minX + sub, minX + sub + G, ... whole.  keep(k, octave) is the caller's per-candidate filter,
+// run before the distance.  Returns the first lowest distance in window order to every lane of the
+// group (*best_idx = -1, distance 256 when nothing survives); *any: the area held a keypoint at all.
+// A column belongs to one lane, which meets its entries in order and keeps the first of equal
+// distances; between lanes the column decides, so the key is distance << 6 | column.  A lane that
+// saw a keypoint and kept none holds kAreaSeen, above every real key and below "nothing at all".
+constexpr uint32_t kAreaNone = 0xFFFFFFFFu, kAreaSeen = 0xFFFFFFFEu;
+
+// One step of the group's minimum by a DPP move within the row of 16 (no LDS round trip): the
+// lower key of this lane and its partner under kCtrl, with the key's keypoint.
+template <int kCtrl>
+__device__ inline void dpp_lower_key(uint32_t& key, int& idx) {
+    const uint32_t ok = (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, kCtrl, 0xF, 0xF, false);
+    const int oi = __builtin_amdgcn_update_dpp(idx, idx, kCtrl, 0xF, 0xF, false);
+    if (ok < key) key = ok, idx = oi;
+}
+
+template <int G, class Args, class Keep>
+__device__ inline int walk_area_group(const Args& a, const FrameView& F, float x, float y, float rs, int sub,
+                                      const uint32_t q[8], Keep keep, int* best_idx, bool* any) {
+    static_assert(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "a group lies within a DPP row");
+    uint32_t key = kAreaNone;
+    int idx = -1;
+    CellRange r;
+    if (window_cells(a, x, y, rs, &r)) {
+        for (int ix = r.minX + sub; ix <= r.maxX; ix += G) {
+            const int j1 = F.cs[ix * kGridRows + r.maxY + 1];
+            for (int j = F.cs[ix * kGridRows + r.minY]; j < j1; ++j) {
+                const int k = F.ci[j];
+                const float2 p = *reinterpret_cast<const float2*>(F.xy + 2LL * k);
+                if (!(fabsf(p.x - x) < rs && fabsf(p.y - y) < rs)) continue;
+                key = min(key, kAreaSeen);
+                if (!keep(k, octave_of(F, k))) continue;
+                const uint32_t kk = ((uint32_t)hamming32(q, F.desc + 32LL * k) << 6) | (uint32_t)ix;
+                if (kk < key) key = kk, idx = k;
+            }
+        }
+    }
+    // after each step the lanes that exchanged agree, so the mirrors pair what xor 4 and xor 8 would
+    if (G >= 2) dpp_lower_key<0xB1>(key, idx);    // quad_perm [1, 0, 3, 2]
+    if (G >= 4) dpp_lower_key<0x4E>(key, idx);    // quad_perm [2, 3, 0, 1]
+    if (G >= 8) dpp_lower_key<0x141>(key, idx);   // row_half_mirror
+    if (G >= 16) dpp_lower_key<0x140>(key, idx);  // row_mirror
+    *best_idx = idx;
+    *any = key != kAreaNone;
+    return idx >= 0 ? (int)(key >> 6) : 256;
 }
 
 // The frame's buffers: a.xy_un / kps / cell_start / cell_idx / desc over batch image img.

@@ -343,3 +343,113 @@ def reloc_points(xy_un, kps, desc, K, pose, n=1000, seed=0, th=10.0, bounds=(0.0
             d[i] = np.packbits(b)
     out["desc"] = d
     return out
+
+
+def fuse_points(xy_un, kps, desc, K, pose, uright=None, bf=None, n=1000, seed=0, th=3.0,
+                bounds=(0.0, 640.0, 0.0, 480.0), pool=None, nlevels=8, scale_factor=1.2, z_range=(1.0, 20.0),
+                invalid=0.04, behind=0.03, outside=0.04, too_near=0.03, too_far=0.03, bad_normal=0.04, empty=0.04,
+                not_finite=0.01, chi=0.10, level_offsets=(0, 0, 0, 0, 1, 1, -1, 2), over_top=0.02,
+                flips=(0, 2, 5, 10, 20, 35, 45, 60, 80, 120)):
+    """Synthetic map points for ORBmatcher::Fuse (a FUSE_POINT_DTYPE array): the frame's keypoints
+    (xy_un, kps: KEYPOINT_DTYPE, desc) back-projected through the inverse of pose = (Rcw 3x3, tcw 3)
+    at a depth from `z_range` -- with uright and bf the depth bf / (x - uright) where the keypoint
+    has a right coordinate, so that the stereo reprojection error follows the image offset -- with
+    sub-radius position noise and `flips` flipped descriptor bits.  The normal is the viewing
+    direction turned by up to 55 degrees.  The predicted level is steered through max_distance as
+    in reloc_points: level = the keypoint's octave plus one of `level_offsets` (Fuse keeps octaves
+    level - 1 and level, so offsets 0 and 1 reach the keypoint and -1 and 2 have it filtered).
+    Several points aim at each of `pool` keypoints (default n // 2).  Mixed in by the given shares,
+    one kind of miss each: invalid points, points behind the camera, projections outside the
+    bounds (every side in turn), points nearer than 0.8 min_distance, farther than 1.2
+    max_distance, normals turned 70 to 180 degrees away, points aimed at a place of the image with
+    no keypoint within the radius (`empty`), not-finite values (a NaN coordinate, a position that
+    overflows the distance, an infinite max_distance, in turn) and, for `chi`, a clean descriptor
+    2.1 to 2.9 sigma of the keypoint's octave to the side: beyond the stereo chi-square limit, and
+    on either side of the monocular one."""
+    from . import FP_VALID, FUSE_POINT_DTYPE
+    rng = np.random.default_rng(seed)
+    xy_un = np.asarray(xy_un, np.float64).reshape(-1, 2)
+    octave = np.asarray(kps["octave"], np.int64)
+    desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    nk = len(octave)
+    out = np.zeros(n, FUSE_POINT_DTYPE)
+    if nk == 0 or n == 0:
+        return out
+    fx, fy, cx, cy = (float(v) for v in K)
+    Rcw = np.asarray(pose[0], np.float64).reshape(3, 3)
+    tcw = np.asarray(pose[1], np.float64).reshape(3)
+    scale = scale_factor ** np.arange(nlevels, dtype=np.float64)
+    npool = max(1, min(nk, n // 2 if pool is None else int(pool)))
+    k = rng.choice(nk, size=npool, replace=False)[rng.integers(0, npool, n)]
+    level = np.clip(octave[k] + rng.choice(list(level_offsets), n), 0, nlevels - 1)
+    nflip = rng.choice(list(flips), n)
+    radius = th * scale[level]
+    uv = xy_un[k] + np.clip(rng.normal(0.0, 0.2, (n, 2)), -0.8, 0.8) * radius[:, None]
+    # the chi-square share: the keypoint's own level, a clean descriptor, an offset along x alone
+    gate = np.flatnonzero(rng.random(n) < chi)
+    level[gate] = octave[k[gate]]
+    nflip[gate] = rng.choice([0, 2, 5], len(gate))
+    uv[gate] = xy_un[k[gate]]
+    uv[gate, 0] += rng.choice([-1.0, 1.0], len(gate)) * rng.uniform(2.1, 2.9, len(gate)) * scale[octave[k[gate]]]
+    # the empty share: a low level, and a place whose nearest keypoint is more than two radii away
+    for i in np.flatnonzero(rng.random(n) < empty):
+        level[i] = rng.integers(0, 2)
+        for _ in range(200):
+            c = np.array([rng.uniform(bounds[0] + 20, bounds[1] - 20), rng.uniform(bounds[2] + 20, bounds[3] - 20)])
+            if np.abs(xy_un - c).max(1).min() > 2.0 * th * scale[level[i]]:
+                uv[i] = c
+                break
+    z = rng.uniform(z_range[0], z_range[1], n)
+    if uright is not None and bf is not None:
+        ur = np.asarray(uright, np.float64)[k]
+        disp = xy_un[k, 0] - ur
+        has = (ur >= 0) & (disp > 0.1)
+        z = np.where(has, bf / np.where(has, disp, 1.0), z)
+    z = np.where(rng.random(n) < behind, -z, z)
+    side = np.flatnonzero(rng.random(n) < outside)
+    far = rng.uniform(50.0, 300.0, len(side))
+    for j, (i, d) in enumerate(zip(side, far)):  # every side in turn
+        if j % 4 == 0:
+            uv[i, 0] = bounds[0] - d
+        elif j % 4 == 1:
+            uv[i, 0] = bounds[1] + d
+        elif j % 4 == 2:
+            uv[i, 1] = bounds[2] - d
+        else:
+            uv[i, 1] = bounds[3] + d
+    pc = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    pw = (pc - tcw) @ Rcw  # Rcw^T (pc - tcw)
+    dist = np.linalg.norm(pc, axis=1)  # |X - Ow|
+    ratio = np.where(level == 0, rng.uniform(0.86, 0.99, n), scale_factor ** (level - 0.5))
+    ratio = np.where(rng.random(n) < over_top, scale_factor ** (nlevels - 1) * 1.1, ratio)
+    maxd = dist * ratio
+    mind = maxd / scale_factor ** (nlevels - 1)
+    mind = np.where(rng.random(n) < too_near, dist * 1.3, mind)
+    maxd = np.where(rng.random(n) < too_far, dist / 1.3, maxd)
+    # the normal: the viewing direction PO / |PO| (in world axes) turned about a random axis across it
+    view = (pc / dist[:, None]) @ Rcw
+    across = np.cross(view, rng.normal(0.0, 1.0, (n, 3)))
+    across /= np.linalg.norm(across, axis=1)[:, None]
+    turn = np.radians(np.where(rng.random(n) < bad_normal, rng.uniform(70.0, 180.0, n), rng.uniform(0.0, 55.0, n)))
+    normal = view * np.cos(turn)[:, None] + across * np.sin(turn)[:, None]
+    for j, i in enumerate(np.flatnonzero(rng.random(n) < not_finite)):  # every kind in turn
+        if j % 3 == 0:
+            pw[i, j % 2] = np.nan
+        elif j % 3 == 1:
+            pw[i] = pw[i] / np.linalg.norm(pw[i]) * 1e30
+            maxd[i], mind[i] = np.inf, 0.0
+        else:
+            maxd[i] = np.inf
+    out["pos"] = pw.astype(np.float32)
+    out["normal"] = normal.astype(np.float32)
+    out["min_distance"] = mind.astype(np.float32)
+    out["max_distance"] = maxd.astype(np.float32)
+    out["flags"] = np.where(rng.random(n) < 1.0 - invalid, FP_VALID, 0)
+    d = desc[k].copy()
+    for i in range(n):
+        if nflip[i]:
+            b = np.unpackbits(d[i])
+            b[rng.choice(256, nflip[i], replace=False)] ^= 1
+            d[i] = np.packbits(b)
+    out["desc"] = d
+    return out
