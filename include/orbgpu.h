@@ -685,9 +685,9 @@ int orbgpu_predict_scale_table(float scale_factor, int nlevels, float* threshold
  * (AddObservation / AddMapPoint), else point first[k] of the list.  *n_points = the list's length,
  * *n_kp = N; ORBGPU_ERR_CAPACITY when cap_points < *n_points or cap_kp < *n_kp (both counts are
  * written first); otherwise errors as for orbgpu_download_bow_matches.
- * Not built: the two-camera form (bRight, NLeft != -1: mvKeys / mvKeysRight, GetRightPose),
- * SearchBySim3 and the Sim3 SearchByProjection overloads, and the host-side Replace / AddObservation
- * bookkeeping. */
+ * Not built: the two-camera form (bRight, NLeft != -1: mvKeys / mvKeysRight, GetRightPose), SearchBySim3
+ * (no caller in LoopClosing.cc), and the host-side Replace / AddObservation bookkeeping.  The Sim3
+ * SearchByProjection overloads follow below. */
 typedef struct {
     float pos[3];        /* pMP->GetWorldPos() */
     float normal[3];     /* pMP->GetNormal() */
@@ -713,6 +713,91 @@ int orbgpu_fuse_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames, const
                       int sim3, void* stream);
 int orbgpu_download_fuse_matches(orbgpu_ctx* ctx, int pair, int32_t* best_idx, int32_t* best_dist, uint8_t* code,
                                  int cap_points, int32_t* first, int cap_kp, int* n_points, int* n_kp, int* nfused);
+
+/* ---- ORBmatcher::SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming) ----
+ * cpp/src/ORBmatcher.cc:428-533, and the overload that also carries vpPointsKFs / vpMatchedKF (:535-647):
+ * the searches LoopClosing::DetectCommonRegionsFromBoW runs on a candidate's covisible points
+ * (LoopClosing.cc:755: th 8, ratio 1.5, the vpPointsKFs form; :777: th 5, ratio 1.0) and
+ * FindMatchesByProjection runs for every keyframe while a loop or merge is being confirmed (:964: th 3,
+ * ratio 1.5), with KeyFrame::GetFeaturesInArea / IsInImage (KeyFrame.cc:706-755) and MapPoint::PredictScale
+ * (MapPoint.cc:516-531), on pinhole keyframes (NLeft == -1: mvKeysUn).
+ * Pair p searches list lists[p] -- the points pts[list_offsets[l], list_offsets[l + 1]), orbgpu_fuse_point
+ * rows -- in batch image frames[p], inside the range of the last orbgpu_undistort_grid_batch, under pose p:
+ * Rcw = Scw.rotationMatrix(), tcw = Scw.translation() / Scw.scale(), Ow = Tcw.inverse().translation()
+ * (:437-438, :544-545).  Each pair is one call of the reference with its own vpMatched: pairs do not see
+ * each other, several pairs may name one list and several pairs one frame (the coarse searches of several
+ * candidates for one current keyframe in one call).  All arithmetic is IEEE single without contraction,
+ * evaluated in the reference's order.  Points are taken in ascending index; each gets one decision code:
+ *   1. ORBGPU_SIM3_SKIPPED: the point lacks ORBGPU_FP_VALID (isBad()) or skip[p][i] is non-zero
+ *      (spAlreadyFound.count(pMP), :452, :560).
+ *   2. ORBGPU_SIM3_NEG_DEPTH: p3Dc = Tcw * X, row by row as ((R0 x + R1 y) + R2 z) + t; zc < 0.0 (:462, :570).
+ *   3. ORBGPU_SIM3_NOT_IN_IMAGE: the projection fails KeyFrame::IsInImage (KeyFrame.cc:752-755), u >= mnMinX
+ *      && u < mnMaxX && v >= mnMinY && v < mnMaxY, half-open; a NaN or infinite projection fails it.  The
+ *      projection is where the overloads differ: projection == ORBGPU_SIM3_PROJECT_DIV is the first one,
+ *      through Pinhole::project (Pinhole.cpp:40-41), u = fx * xc / zc + cx; ORBGPU_SIM3_PROJECT_INVZ is the
+ *      second (:574-579), invz = 1 / zc; x = xc * invz; u = fx * x + cx.  The two round differently: a point
+ *      can be inside the image or a window under one and outside under the other.
+ *   4. ORBGPU_SIM3_DISTANCE: PO = X - Ow; dist = sqrtf((PO.x * PO.x + PO.y * PO.y) + PO.z * PO.z); dist <
+ *      0.8f * min_distance || dist > 1.2f * max_distance (:473-479, MapPoint.cc:504-514).  Deviation, as for
+ *      orbgpu_fuse_batch: a dist or max_distance / dist that is not finite also gets this code.
+ *   5. ORBGPU_SIM3_NORMAL: (PO.x * n.x + PO.y * n.y) + PO.z * n.z < 0.5 * dist, compared in double (:484, :597).
+ *   6. nPredictedLevel = the number of orbgpu_predict_scale_table steps below max_distance / dist; radius =
+ *      th * mvScaleFactors[level] (:487-490; th is an int in the reference, a float here as elsewhere).
+ *   7. ORBGPU_SIM3_EMPTY_WINDOW: KeyFrame::GetFeaturesInArea(u, v, radius), without a level filter, is empty
+ *      (:494).  This is decided before occupancy is looked at: a window whose every keypoint is taken is
+ *      not empty.
+ *   8. over that list in window order (grid column, row, index within the cell): a keypoint with
+ *      vpMatched[idx] set -- held before the call (kp_block) or taken earlier in this call -- is passed over
+ *      (:505, :618); an octave outside [level - 1, level] is passed over (:510); the best is the first lowest
+ *      Hamming distance, strict < from 256.
+ *   9. ORBGPU_SIM3_MATCHED when (float)bestDist <= 50.0f * ratio_hamming (TH_LOW * ratioHamming, :524: the
+ *      product is a float and so is the compare): vpMatched[bestIdx] = pMP, the keypoint is taken, nmatches++.
+ *      Otherwise ORBGPU_SIM3_NOT_MATCHED, also when every candidate was passed over; such a point takes nothing.
+ * The reference would write vpMatched[-1] if the limit reached 256, so such a ratio_hamming is refused.
+ * Parity with the reference is unpinned, as for the other matcher functions: the yardstick is the Python
+ * restatement in tests/test_sim3_projection.py.
+ * skip ([n_pairs][skip_stride] u8, host; NULL: none) as for orbgpu_fuse_batch; kp_block ([n_pairs][kp_stride]
+ * u8, host; NULL: none): [p][k] != 0 where vpMatched[k] is set before the call.  K = {fx, fy, cx, cy}.  Host
+ * arrays are pageable and may be reused when the call returns.
+ * ORBGPU_ERR_INVALID: null context, n_pairs < 0 or above the context's image capacity, null arrays with work
+ * to do, a frame outside the gridded range, lists[p] outside [0, n_lists), list_offsets not ascending from a
+ * value >= 0, skip_stride below a named list's length, kp_stride below a frame's keypoint count, th negative
+ * or not finite, ratio_hamming not finite or 50.0f * ratio_hamming outside [0, 256), projection outside
+ * {0, 1}.  ORBGPU_ERR_CAPACITY: a list above ORBGPU_FUSE_MAX_POINTS, or a keypoint capacity above the resolve
+ * kernel's LDS budget.  n_pairs == 0 succeeds and leaves no pair to download.  Every status is decided before
+ * any launch.  The results live in buffers of their own: they outlive the other searches' calls and leave
+ * the other searches' results alone.
+ * orbgpu_download_sim3_matches, per keypoint k of the frame: match[k] = the list index of the point this
+ * call put on k, else -1 (a keypoint held before the call stays -1); the vpMatchedKF of the second overload
+ * needs nothing more: vpMatchedKF[k] = vpPointsKFs[match[k]] (:640).  Per point of the pair's list: code[i];
+ * best_idx[i] = the keypoint when matched, else -1; best_dist[i] = its distance when matched, else 256.
+ * *nmatches = the reference's return value.  *n_kp = N, *n_points = the list's length; ORBGPU_ERR_CAPACITY
+ * when cap_kp < *n_kp or cap_points < *n_points (both counts are written first); otherwise errors as for
+ * orbgpu_download_bow_matches.
+ * orbgpu_sim3_replay_stats (measurement, tools/sim3_search_time.py): what the replay of pair `pair` did:
+ * {points that reached it, passes, lanes found stale over all passes, windows walked again}.
+ * Not built: the two-camera form (NLeft != -1), SearchByBoW(KeyFrame*, KeyFrame*), SearchBySim3, and the
+ * Sim3Solver / Optimizer::OptimizeSim3 between the calls. */
+#define ORBGPU_SIM3_PROJECT_DIV 0  /* :428, Pinhole::project */
+#define ORBGPU_SIM3_PROJECT_INVZ 1 /* :535, the invz form */
+#define ORBGPU_SIM3_SKIPPED 1
+#define ORBGPU_SIM3_NEG_DEPTH 2
+#define ORBGPU_SIM3_NOT_IN_IMAGE 3
+#define ORBGPU_SIM3_DISTANCE 4
+#define ORBGPU_SIM3_NORMAL 5
+#define ORBGPU_SIM3_EMPTY_WINDOW 6
+#define ORBGPU_SIM3_NOT_MATCHED 7
+#define ORBGPU_SIM3_MATCHED 8
+
+int orbgpu_sim3_search_by_projection_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames, const int32_t* lists,
+                                           int n_lists, const orbgpu_fuse_point* pts, const int32_t* list_offsets,
+                                           const orbgpu_reloc_pose* poses, const float K[4], const uint8_t* skip,
+                                           int skip_stride, const uint8_t* kp_block, int kp_stride, float th,
+                                           float ratio_hamming, int projection, void* stream);
+int orbgpu_download_sim3_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int cap_kp, int32_t* best_idx,
+                                 int32_t* best_dist, uint8_t* code, int cap_points, int* n_kp, int* n_points,
+                                 int* nmatches);
+int orbgpu_sim3_replay_stats(orbgpu_ctx* ctx, int pair, int32_t stats[4]);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

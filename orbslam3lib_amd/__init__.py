@@ -65,6 +65,11 @@ FUSE_MAX_POINTS = 65536  # ORBGPU_FUSE_MAX_POINTS
 # ORBGPU_FUSE_*: the decision a point ended with (the reference's count_* counters, ORBmatcher.cc:1183)
 (FUSE_SKIPPED, FUSE_NEG_DEPTH, FUSE_NOT_IN_IMAGE, FUSE_DISTANCE, FUSE_NORMAL, FUSE_EMPTY_WINDOW, FUSE_ABOVE_TH_LOW,
  FUSE_FUSED) = range(1, 9)
+# ORBGPU_SIM3_*: the decision a point of sim3_search_by_projection ended with (1 to 6 are the FUSE_* values),
+# and the projection of each overload (ORBmatcher.cc:428: Pinhole::project; :535: the invz form)
+(SIM3_SKIPPED, SIM3_NEG_DEPTH, SIM3_NOT_IN_IMAGE, SIM3_DISTANCE, SIM3_NORMAL, SIM3_EMPTY_WINDOW, SIM3_NOT_MATCHED,
+ SIM3_MATCHED) = range(1, 9)
+SIM3_PROJECT_DIV, SIM3_PROJECT_INVZ = 0, 1
 
 # cv::KeyPoint layout (28 B)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -93,6 +98,7 @@ EXPORTED = [
     "orbgpu_reloc_by_projection_batch", "orbgpu_download_reloc_matches", "orbgpu_predict_scale_table",
     "orbgpu_search_for_triangulation_batch", "orbgpu_download_triangulation_matches",
     "orbgpu_fuse_batch", "orbgpu_download_fuse_matches",
+    "orbgpu_sim3_search_by_projection_batch", "orbgpu_download_sim3_matches", "orbgpu_sim3_replay_stats",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -991,6 +997,62 @@ class BatchExtractor:
         _check(_lib.orbgpu_download_fuse_matches(self.ctx.handle, pair, _p(bi), _p(bd), _p(cd), cap_points, _p(first),
                                                  cap_kp, C.byref(n), C.byref(nk), C.byref(nf)))
         return bi[:n.value], bd[:n.value], cd[:n.value], first[:nk.value], nf.value
+
+    def sim3_search_by_projection(self, frames, lists, point_lists, poses, K, skip=None, kp_block=None, th=8.0,
+                                  ratio_hamming=1.5, projection=SIM3_PROJECT_DIV, stream=None):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:
+        428-533; projection = SIM3_PROJECT_DIV) and the overload with vpPointsKFs / vpMatchedKF (:535-647;
+        SIM3_PROJECT_INVZ), LoopClosing::DetectCommonRegionsFromBoW / FindMatchesByProjection; pinhole
+        keyframes, for pairs of a list of map points and a batch image after undistort_grid().  frames,
+        lists, point_lists (FUSE_POINT_DTYPE), poses (RELOC_POSE_DTYPE rows from Scw: Rcw, tcw / s, Ow), K
+        and skip (spAlreadyFound) as for fuse; kp_block: optional list (one per pair) of u8 arrays, or one
+        2-D array (non-zero = vpMatched[k] is set before the call).  Each pair is one call of the
+        reference with its own vpMatched."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        ls = np.ascontiguousarray(lists, np.int32).reshape(-1)
+        npairs = len(fr)
+        if len(ls) != npairs:
+            raise ValueError("one list index per pair")
+        if isinstance(point_lists, tuple):
+            pts, off, nl = self._map_point_rows(point_lists, FUSE_POINT_DTYPE, len(point_lists[1]) - 1)
+        else:
+            pts, off, nl = self._map_point_rows(point_lists, FUSE_POINT_DTYPE)
+        ps = np.ascontiguousarray(poses, RELOC_POSE_DTYPE).reshape(-1)
+        if len(ps) != npairs:
+            raise ValueError("one pose per pair")
+        Kf = np.ascontiguousarray(K, dtype=np.float32).reshape(4)
+        sk, stride = self._pad_rows(skip, np.uint8, 0)
+        if sk is not None and sk.shape[0] != npairs:
+            raise ValueError("one row of skip flags per pair")
+        blk, kstride = self._pad_rows(kp_block, np.uint8, 0)
+        if blk is not None and blk.shape[0] != npairs:
+            raise ValueError("one row of occupancy per pair")
+        _check(_lib.orbgpu_sim3_search_by_projection_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(ls) if npairs else None, nl,
+            _p(pts) if len(pts) else None, _p(off), _p(ps) if npairs else None, _p(Kf),
+            _p(sk) if sk is not None and npairs else None, stride, _p(blk) if blk is not None and npairs else None,
+            kstride, C.c_float(th), C.c_float(ratio_hamming), int(projection), C.c_void_p(stream) if stream else None))
+
+    def sim3_matches(self, pair, cap_points=FUSE_MAX_POINTS, cap_kp=65536):
+        """(match [N] int32: for each keypoint of the frame the list index of the point this call put on
+        it, -1 if none (vpMatchedKF[k] = vpPointsKFs[match[k]]); best_idx [n] int32: the keypoint point i
+        matched, else -1; best_dist [n] int32: its distance when matched, else 256; code [n] uint8:
+        SIM3_*; nmatches) of pair `pair` of the last sim3_search_by_projection."""
+        m = np.zeros(cap_kp, np.int32)
+        bi = np.zeros(cap_points, np.int32)
+        bd = np.zeros(cap_points, np.int32)
+        cd = np.zeros(cap_points, np.uint8)
+        nk, n, nm = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_sim3_matches(self.ctx.handle, pair, _p(m), cap_kp, _p(bi), _p(bd), _p(cd), cap_points,
+                                                 C.byref(nk), C.byref(n), C.byref(nm)))
+        return m[:nk.value], bi[:n.value], bd[:n.value], cd[:n.value], nm.value
+
+    def sim3_replay_stats(self, pair):
+        """(points that reached the replay, passes, lanes found stale over all passes, windows walked
+        again) of pair `pair` of the last sim3_search_by_projection: what tools/sim3_search_time.py prints."""
+        s = np.zeros(4, np.int32)
+        _check(_lib.orbgpu_sim3_replay_stats(self.ctx.handle, pair, _p(s)))
+        return tuple(int(v) for v in s)
 
     def undistort_grid(self, K, dist=(), stream=None):
         """Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:405-436, 741-825) for every

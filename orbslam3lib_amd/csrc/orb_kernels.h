@@ -693,6 +693,52 @@ struct FuseArgs {
 };
 hipError_t launch_fuse(const FuseArgs& a, int npairs, int max_pts, hipStream_t st);
 
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) and the vpPointsKFs
+// overload on pinhole keyframes (orb_sim3.hip).  The points are FusePoint rows, the poses RelocPose rows,
+// the candidate records RelocCand (n: within the limit, in the band and free before the call; -1: the
+// point ended before the loop).
+enum Sim3Code : uint8_t {  // ORBGPU_SIM3_*: 1..6 are the FuseCode values
+    kSim3Pending = 0,      // between the two kernels: the replay decides
+    kSim3NotMatched = 7, kSim3Matched = 8
+};
+constexpr int kSim3ProjectDiv = 0, kSim3ProjectInvz = 1;  // ORBGPU_SIM3_PROJECT_*
+struct Sim3Args {
+    const int32_t* frames;    // [pair] the batch image that is pKF
+    const int32_t* lists;     // [pair] the list the pair searches
+    const int32_t* out_off;   // [pair + 1] the pair's rows of cand / order / best_idx / best_dist / code
+    const int32_t* list_off;  // [list + 1], list_off[0] == 0
+    const FusePoint* pts;     // all lists' points
+    const RelocPose* poses;   // [pair]
+    const uint8_t* skip;      // [pair][skip_stride] non-zero: spAlreadyFound holds the point; or nullptr
+    int skip_stride;
+    const uint8_t* kp_block;  // [pair][out_cap] vpMatched[k] set before the call, or nullptr
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const float* xy_un;       // grid buffers (orbgpu_undistort_grid_batch)
+    const int32_t* cell_start;
+    const int32_t* cell_idx;
+    const uint8_t* desc;      // out_desc
+    float bounds[4], grid_inv[2];
+    float scale[kMaxLevels];
+    float level_step[kMaxLevels];  // predict_scale_table, as in RelocArgs
+    int nlevels;
+    float K[4], th;
+    float limit;              // TH_LOW * ratioHamming, the float product (:524)
+    int projection;           // kSim3ProjectDiv / kSim3ProjectInvz
+    RelocCand* cand;          // [point row]
+    int32_t* order;           // [point row] the pair's pending points, ascending (k_sim3_resolve's own)
+    int32_t* best_idx;        // [point row]
+    int32_t* best_dist;       // [point row]
+    uint8_t* code;            // [point row]
+    int32_t* match;           // [pair][out_cap]
+    int32_t* nmatches;        // [pair]
+    int32_t* stats;           // [pair][kSim3Stats]: pending points, passes, stale lanes, fresh walks
+};
+constexpr int kSim3Stats = 4;
+size_t sim3_resolve_lds_bytes(int out_cap);
+hipError_t launch_sim3(const Sim3Args& a, int npairs, int max_pts, hipStream_t st);
+
 hipError_t launch_sbs_split(const SbsArgs& a, hipStream_t st);
 hipError_t launch_pack_soa(const SoaArgs& a, int npairs, hipStream_t st);
 // orbgpu_export_batch (orb_io.hip k_pack_export): the produced rows of a batch, packed

@@ -1,8 +1,8 @@
 // orb_matchers.cpp -- the part of the C ABI (include/orbgpu.h) that runs the ORBmatcher searches over
 // the device-resident results of a batch: the local-map search (orb_sbp.hip), the motion-model search
 // (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip), the
-// triangulation search (orb_tri.hip), the relocalisation search (orb_reloc.hip) and the map-point fusion
-// (orb_fuse.hip).  Every entry
+// triangulation search (orb_tri.hip), the relocalisation search (orb_reloc.hip), the map-point fusion
+// (orb_fuse.hip) and the loop closer's Sim3 projection searches (orb_sim3.hip).  Every entry
 // point validates its own arguments and lays out its own buffers; what they share -- the offsets check, the padded row uploads, the common
 // argument fields, the launch path and the download -- is written once, below.
 #include <cmath>
@@ -313,6 +313,71 @@ void predict_scale_table(float scale_factor, int nlevels, float* thresholds) {
         }
         thresholds[n] = as_float(lo);
     }
+}
+
+// What orbgpu_fuse_batch and orbgpu_sim3_search_by_projection_batch share: pairs of a batch image and a list
+// of points.  head = frames [np], lists [np], the pairs' output rows [np + 1], the list offsets rebased to 0
+// [nl + 1]; rows = the output rows of all pairs; max_pts = the longest list a pair names; skip_pitch = the
+// device pitch of the skip rows.
+struct ListPairs {
+    std::vector<int32_t> head;
+    int max_pts = 0, total_pts = 0;
+    size_t rows = 0, skip_pitch = 1;
+};
+
+// The checks on those arguments, in orbgpu_fuse_batch's order (pair_check(p): the caller's own test of pair
+// p), then the head.  n_pairs == 0 passes with an empty head.
+template <class PairCheck>
+int check_list_pairs(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const int32_t* lists, int n_lists,
+                     const void* pts, const int32_t* list_offsets, const void* poses, const float* K,
+                     const uint8_t* skip, int skip_stride, ListPairs* lp, PairCheck&& pair_check) {
+    if (n_pairs > 0 && (!frames || !lists || !list_offsets || !poses || !K)) return fail(ORBGPU_ERR_INVALID, "null array");
+    if (n_pairs > 0 && n_lists < 1) return fail(ORBGPU_ERR_INVALID, "no lists");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (frames[p] < 0 || frames[p] >= c->grid_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
+        if (lists[p] < 0 || lists[p] >= n_lists) return fail(ORBGPU_ERR_INVALID, "list outside [0, n_lists)");
+        if (int e = pair_check(p)) return e;
+    }
+    int max_list = 0;
+    if (n_pairs > 0)
+        if (int e = check_offsets(list_offsets, n_lists, true, "list_offsets", &max_list, &lp->total_pts)) return e;
+    if (lp->total_pts > 0 && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
+    for (int p = 0; p < n_pairs; ++p)  // over the lists the pairs name
+        lp->max_pts = std::max(lp->max_pts, list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
+    if (n_pairs > 0 && skip && skip_stride < lp->max_pts) return fail(ORBGPU_ERR_INVALID, "skip_stride below a list's length");
+    if (max_list > kFuseMaxPoints) return fail(ORBGPU_ERR_CAPACITY, "a list holds more than ORBGPU_FUSE_MAX_POINTS points");
+    if ((long long)n_pairs * lp->max_pts > INT32_MAX) return fail(ORBGPU_ERR_CAPACITY, "more point rows than an int32 counts");
+    if (n_pairs == 0) return 0;
+    const size_t np = (size_t)n_pairs, nl = (size_t)n_lists;
+    std::vector<int32_t>& head = lp->head;
+    head.resize(3 * np + 1 + nl + 1);
+    std::copy(frames, frames + np, head.begin());
+    std::copy(lists, lists + np, head.begin() + np);
+    head[2 * np] = 0;
+    for (size_t p = 0; p < np; ++p)
+        head[2 * np + p + 1] = head[2 * np + p] + (list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
+    for (size_t l = 0; l <= nl; ++l) head[3 * np + 1 + l] = list_offsets[l] - list_offsets[0];
+    lp->rows = (size_t)head[3 * np];  // at most max_images * ORBGPU_FUSE_MAX_POINTS
+    lp->skip_pitch = (size_t)std::max(lp->max_pts, 1);
+    return 0;
+}
+
+// The point side of a download (fuse, sim3): pair `pair`'s rows of the three arrays that lie one after the
+// other on the device, best_idx [rows], best_dist [rows], code [rows], after the keypoint side `r` has
+// written its count: both counts are out before either capacity is judged.
+int download_point_rows(orbgpu_ctx* c, const std::vector<int32_t>& off, int pair, int r, const int32_t* didx,
+                        int32_t* best_idx, int32_t* best_dist, uint8_t* code, int cap_points, int* n_points) {
+    const size_t rows = (size_t)off.back(), row0 = (size_t)off[(size_t)pair];
+    const int n = off[(size_t)pair + 1] - off[(size_t)pair];
+    if (n_points) *n_points = n;
+    if (r && r != ORBGPU_ERR_CAPACITY) return r;
+    if (n > cap_points) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small (points)");
+    if (r) return r;
+    if (best_idx && n) D2H(best_idx, didx + row0, 4 * (size_t)n);
+    if (best_dist && n) D2H(best_dist, didx + rows + row0, 4 * (size_t)n);
+    if (code && n) D2H(code, reinterpret_cast<const uint8_t*>(didx + 2 * rows) + row0, (size_t)n);
+    return ORBGPU_OK;
 }
 
 }  // namespace
@@ -745,40 +810,23 @@ int orbgpu_fuse_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const i
     if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ORBGPU_ERR_INVALID, "th negative or not finite");
     const bool gate = sim3 == 0, stereo = gate && use_uright != 0;
     if (gate && (!(bf >= 0.0f) || !std::isfinite(bf))) return fail(ORBGPU_ERR_INVALID, "bf negative or not finite");
-    if (n_pairs > 0 && (!frames || !lists || !list_offsets || !poses || !K)) return fail(ORBGPU_ERR_INVALID, "null array");
-    if (n_pairs > 0 && n_lists < 1) return fail(ORBGPU_ERR_INVALID, "no lists");
-    for (int p = 0; p < n_pairs; ++p) {
-        if (frames[p] < 0 || frames[p] >= c->grid_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
-        if (lists[p] < 0 || lists[p] >= n_lists) return fail(ORBGPU_ERR_INVALID, "list outside [0, n_lists)");
-        if (stereo && ((frames[p] & 1) || frames[p] / 2 >= c->stereo_pairs))
-            return fail(ORBGPU_ERR_INVALID, "mvuRight needs the left image of a pair of the last stereo_matches_batch");
-    }
-    int max_list = 0, total_pts = 0;
-    if (n_pairs > 0)
-        if (int e = check_offsets(list_offsets, n_lists, true, "list_offsets", &max_list, &total_pts)) return e;
-    if (total_pts > 0 && !pts) return fail(ORBGPU_ERR_INVALID, "null points");
-    int max_pts = 0;  // over the lists the pairs name
-    for (int p = 0; p < n_pairs; ++p) max_pts = std::max(max_pts, list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
-    if (n_pairs > 0 && skip && skip_stride < max_pts) return fail(ORBGPU_ERR_INVALID, "skip_stride below a list's length");
-    if (max_list > kFuseMaxPoints) return fail(ORBGPU_ERR_CAPACITY, "a list holds more than ORBGPU_FUSE_MAX_POINTS points");
-    if ((long long)n_pairs * max_pts > INT32_MAX) return fail(ORBGPU_ERR_CAPACITY, "more point rows than an int32 counts");
+    ListPairs lp;
+    if (int e = check_list_pairs(c, n_pairs, frames, lists, n_lists, pts, list_offsets, poses, K, skip, skip_stride, &lp,
+                                 [&](int p) {
+                                     if (stereo && ((frames[p] & 1) || frames[p] / 2 >= c->stereo_pairs))
+                                         return fail(ORBGPU_ERR_INVALID, "mvuRight needs the left image of a pair of the last stereo_matches_batch");
+                                     return 0;
+                                 }))
+        return e;
     if (n_pairs == 0) {
         c->fuse_cover.image.clear();
         c->fuse_off.clear();
         return ORBGPU_OK;
     }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nl = (size_t)n_lists, total = (size_t)total_pts;
-    // fusein: frames [np], lists [np], the pairs' output rows [np + 1], the list offsets rebased to 0 [nl + 1]
-    std::vector<int32_t> head(3 * np + 1 + nl + 1);
-    std::copy(frames, frames + np, head.begin());
-    std::copy(lists, lists + np, head.begin() + np);
-    head[2 * np] = 0;
-    for (size_t p = 0; p < np; ++p)
-        head[2 * np + p + 1] = head[2 * np + p] + (list_offsets[lists[p] + 1] - list_offsets[lists[p]]);
-    for (size_t l = 0; l <= nl; ++l) head[3 * np + 1 + l] = list_offsets[l] - list_offsets[0];
-    const size_t rows = (size_t)head[3 * np];  // at most max_images * ORBGPU_FUSE_MAX_POINTS
-    const size_t skip_pitch = (size_t)std::max(max_pts, 1);
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, total = (size_t)lp.total_pts;
+    const std::vector<int32_t>& head = lp.head;
+    const size_t rows = lp.rows, skip_pitch = lp.skip_pitch;
+    const int max_pts = lp.max_pts;
     HIP_TRY(hipSetDevice(c->device));
     if (c->fusein.ensure(head.size() * 4 + 256) || c->fusept.ensure(total * sizeof(FusePoint) + 256) ||
         c->fusepose.ensure(np * sizeof(RelocPose) + 256) || (skip && c->fuseskip.ensure(np * skip_pitch + 256)) ||
@@ -830,19 +878,126 @@ int orbgpu_fuse_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const i
 int orbgpu_download_fuse_matches(orbgpu_ctx* c, int pair, int32_t* best_idx, int32_t* best_dist, uint8_t* code,
                                  int cap_points, int32_t* first, int cap_kp, int* n_points, int* n_kp, int* nfused) {
     if (!c || pair < 0 || (size_t)pair >= c->fuse_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    const size_t rows = (size_t)c->fuse_off.back(), row0 = (size_t)c->fuse_off[(size_t)pair];
-    const int n = c->fuse_off[(size_t)pair + 1] - c->fuse_off[(size_t)pair];
-    if (n_points) *n_points = n;
     // the keypoint side first: both counts are out before either capacity is judged
     const int r = download_matches(c, c->fuse_cover, pair, "bad pair", c->fusefirst.as<int32_t>(), c->fusenf.as<int32_t>(),
                                    row_cap(c, false), first, cap_kp, n_kp, nfused, nullptr);
-    if (r && r != ORBGPU_ERR_CAPACITY) return r;
-    if (n > cap_points) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small (points)");
+    return download_point_rows(c, c->fuse_off, pair, r, c->fuseout.as<int32_t>(), best_idx, best_dist, code, cap_points,
+                               n_points);
+}
+
+// ---- ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
+// on pinhole keyframes (orb_sim3.hip) ----
+static_assert(ORBGPU_SIM3_SKIPPED == kFuseSkipped && ORBGPU_SIM3_NEG_DEPTH == kFuseNegDepth &&
+                  ORBGPU_SIM3_NOT_IN_IMAGE == kFuseNotInImage && ORBGPU_SIM3_DISTANCE == kFuseDistance &&
+                  ORBGPU_SIM3_NORMAL == kFuseNormal && ORBGPU_SIM3_EMPTY_WINDOW == kFuseEmptyWindow &&
+                  ORBGPU_SIM3_NOT_MATCHED == kSim3NotMatched && ORBGPU_SIM3_MATCHED == kSim3Matched &&
+                  ORBGPU_SIM3_PROJECT_DIV == kSim3ProjectDiv && ORBGPU_SIM3_PROJECT_INVZ == kSim3ProjectInvz,
+              "the header states the decision codes and the projection forms");
+
+int orbgpu_sim3_search_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const int32_t* lists,
+                                           int n_lists, const orbgpu_fuse_point* pts, const int32_t* list_offsets,
+                                           const orbgpu_reloc_pose* poses, const float K[4], const uint8_t* skip,
+                                           int skip_stride, const uint8_t* kp_block, int kp_stride, float th,
+                                           float ratio_hamming, int projection, void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ORBGPU_ERR_INVALID, "th negative or not finite");
+    const float limit = 50.0f * ratio_hamming;  // TH_LOW * ratioHamming (:524): int * float, a float
+    if (!std::isfinite(ratio_hamming) || !(limit >= 0.0f && limit < 256.0f))
+        return fail(ORBGPU_ERR_INVALID, "ratio_hamming not finite or 50 * ratio_hamming outside [0, 256) (256 would match keypoint -1)");
+    if (projection != ORBGPU_SIM3_PROJECT_DIV && projection != ORBGPU_SIM3_PROJECT_INVZ)
+        return fail(ORBGPU_ERR_INVALID, "projection is ORBGPU_SIM3_PROJECT_DIV or ORBGPU_SIM3_PROJECT_INVZ");
+    // the context's own limit, whatever the batch holds: a pair count above 0 is enough to meet it
+    if (n_pairs > 0 && sim3_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
+        return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
+    ListPairs lp;
+    if (int e = check_list_pairs(c, n_pairs, frames, lists, n_lists, pts, list_offsets, poses, K, skip, skip_stride, &lp,
+                                 [](int) { return 0; }))
+        return e;
+    if (n_pairs > 0 && kp_block && kp_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative kp_stride");
+    if (n_pairs == 0) {
+        c->sim3_cover.image.clear();
+        c->sim3_off.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, total = (size_t)lp.total_pts;
+    if (kp_block)  // one row of kp_stride flags per pair: it must cover the frame's keypoints
+        if (int e = rows_cover_counts(c, c->grid_images, frames, 1, n_pairs, kp_stride,
+                                      "kp_stride below the frame's keypoint count"))
+            return e;
+    const std::vector<int32_t>& head = lp.head;
+    const size_t rows = lp.rows, skip_pitch = lp.skip_pitch;
+    HIP_TRY(hipSetDevice(c->device));
+    // sim3out: best_idx, best_dist [rows each], code [rows] (the three download_point_rows reads), then,
+    // 4-byte aligned, the replay's order [rows]
+    const size_t order_at = (rows * 9 + 3) & ~(size_t)3;
+    if (c->sim3in.ensure(head.size() * 4 + 256) || c->sim3pt.ensure(total * sizeof(FusePoint) + 256) ||
+        c->sim3pose.ensure(np * sizeof(RelocPose) + 256) || (skip && c->sim3skip.ensure(np * skip_pitch + 256)) ||
+        (kp_block && c->sim3blk.ensure(np * cap + 256)) || c->sim3cand.ensure(rows * sizeof(RelocCand) + 256) ||
+        c->sim3out.ensure(order_at + rows * 4 + 256) || c->sim3match.ensure(np * cap * 4 + 256) ||
+        c->sim3nm.ensure(np * (1 + kSim3Stats) * 4 + 256))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (Sim3 projection search)");
+    Sim3Args a{};
+    a.frames = c->sim3in.as<int32_t>();
+    a.lists = a.frames + np;
+    a.out_off = a.lists + np;
+    a.list_off = a.out_off + np + 1;
+    a.pts = c->sim3pt.as<FusePoint>();
+    a.poses = c->sim3pose.as<RelocPose>();
+    a.skip = skip ? c->sim3skip.as<uint8_t>() : nullptr;
+    a.skip_stride = (int)skip_pitch;
+    a.kp_block = kp_block ? c->sim3blk.as<uint8_t>() : nullptr;
+    bind_frame(a, c);
+    bind_grid(a, c);
+    bind_scale(a, c);
+    predict_scale_table(c->prm.scale_factor, c->prm.nlevels, a.level_step);  // MapPoint.cc:516-531
+    for (int k = 0; k < 4; ++k) a.K[k] = K[k];
+    a.th = th;
+    a.limit = limit;
+    a.projection = projection;
+    a.cand = c->sim3cand.as<RelocCand>();
+    a.best_idx = c->sim3out.as<int32_t>();
+    a.best_dist = a.best_idx + rows;
+    a.code = reinterpret_cast<uint8_t*>(a.best_dist + rows);
+    a.order = reinterpret_cast<int32_t*>(c->sim3out.as<uint8_t>() + order_at);
+    a.match = c->sim3match.as<int32_t>();
+    a.nmatches = c->sim3nm.as<int32_t>();
+    a.stats = a.nmatches + np;
+    const int r = run_search(
+        c, stream,
+        [&](hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(c->sim3in.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
+            if (total)
+                HIP_TRY(hipMemcpyAsync(c->sim3pt.p, pts + list_offsets[0], total * sizeof(FusePoint), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(c->sim3pose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
+            if (skip)
+                if (int e = upload_rows(c->sim3skip.p, skip_pitch, skip, (size_t)skip_stride, (size_t)lp.max_pts, np, 0, s))
+                    return e;
+            if (kp_block) return upload_rows(c->sim3blk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), np, 0, s);
+            return 0;
+        },
+        [&](hipStream_t s) { return launch_sim3(a, n_pairs, lp.max_pts, s); });
     if (r) return r;
-    const int32_t* didx = c->fuseout.as<int32_t>();
-    if (best_idx && n) D2H(best_idx, didx + row0, 4 * (size_t)n);
-    if (best_dist && n) D2H(best_dist, didx + rows + row0, 4 * (size_t)n);
-    if (code && n) D2H(code, reinterpret_cast<const uint8_t*>(didx + 2 * rows) + row0, (size_t)n);
+    set_cover(c->sim3_cover, np, frames, 1, false);
+    c->sim3_off.assign(head.begin() + 2 * np, head.begin() + 3 * np + 1);
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_sim3_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap_kp, int32_t* best_idx,
+                                 int32_t* best_dist, uint8_t* code, int cap_points, int* n_kp, int* n_points,
+                                 int* nmatches) {
+    if (!c || pair < 0 || (size_t)pair >= c->sim3_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    const int r = download_matches(c, c->sim3_cover, pair, "bad pair", c->sim3match.as<int32_t>(), c->sim3nm.as<int32_t>(),
+                                   row_cap(c, false), match, cap_kp, n_kp, nmatches, nullptr);
+    return download_point_rows(c, c->sim3_off, pair, r, c->sim3out.as<int32_t>(), best_idx, best_dist, code, cap_points,
+                               n_points);
+}
+
+int orbgpu_sim3_replay_stats(orbgpu_ctx* c, int pair, int32_t stats[4]) {
+    static_assert(kSim3Stats == 4, "the header states the count");
+    if (!c || !stats || pair < 0 || (size_t)pair >= c->sim3_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (int e_ = ctx_sync(c)) return e_;
+    D2H(stats, c->sim3nm.as<int32_t>() + c->sim3_cover.image.size() + (size_t)pair * kSim3Stats, 4 * kSim3Stats);
     return ORBGPU_OK;
 }
 

@@ -3,7 +3,8 @@
 // (orb_sbp.hip: the local-map search, orb_track.hip: the motion-model search) and, with
 // ComputeThreeMaxima, by the initialisation search (orb_init.hip); the relocalisation and
 // bag-of-words searches (orb_reloc.hip, orb_bow.hip) share its candidate and rotation-bin helpers,
-// and the fusion (orb_fuse.hip) walks KeyFrame::GetFeaturesInArea, the same cells, by a group of lanes.
+// and the fusion (orb_fuse.hip) and the Sim3 projection searches (orb_sim3.hip) walk
+// KeyFrame::GetFeaturesInArea, the same cells, by a group of lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -204,6 +205,91 @@ __device__ inline void project_pinhole(const float Rcw[9], const float tcw[3], c
     *zc = ((Rcw[6] * X + Rcw[7] * Y) + Rcw[8] * Z) + tcw[2];
     *u = K[0] * *xc / *zc + K[2];
     *v = K[1] * *yc / *zc + K[3];
+}
+
+// The same transform with the projection the vpPointsKFs overload of the Sim3 SearchByProjection writes out
+// (ORBmatcher.cc:574-579): invz = 1 / zc; x = xc * invz; u = fx * x + cx.  It rounds three times where
+// Pinhole::project rounds twice, so the two can land a float apart.  Every step is a named single-precision
+// value under contract(off): no fused multiply-add, no reciprocal folded into a division.
+__device__ inline void project_pinhole_invz(const float Rcw[9], const float tcw[3], const float K[4], const float pos[3],
+                                            float* xc, float* yc, float* zc, float* u, float* v) {
+#pragma clang fp contract(off)
+    const float X = pos[0], Y = pos[1], Z = pos[2];
+    *xc = ((Rcw[0] * X + Rcw[1] * Y) + Rcw[2] * Z) + tcw[0];
+    *yc = ((Rcw[3] * X + Rcw[4] * Y) + Rcw[5] * Z) + tcw[1];
+    *zc = ((Rcw[6] * X + Rcw[7] * Y) + Rcw[8] * Z) + tcw[2];
+    const float invz = 1.0f / *zc;
+    const float x = *xc * invz;
+    const float y = *yc * invz;
+    const float fxx = K[0] * x;
+    const float fyy = K[1] * y;
+    *u = fxx + K[2];
+    *v = fyy + K[3];
+}
+
+// KeyFrame::GetFeaturesInArea(x, y, rs) by a group of G adjacent lanes as in walk_area_group, keeping not the
+// best alone but the four lowest (distance, window position) among the keypoints keep(k, octave) lets
+// through whose distance within(d) accepts, and counting them: idx[t] / dist[t] (-1 / 256 where there are
+// fewer) and *n, the same in every lane of the group; *any: the area held a keypoint at all.  A lane meets
+// its columns' entries in window order, so its key is distance << 22 | column << 16 | place in the column's
+// list; keys of different lanes differ in the column.  The group's lists merge by four rounds of "lowest
+// head", the minimum taken by shuffles that stay inside the group.
+template <int G, class Args, class Keep, class Within>
+__device__ inline void walk_area_group_top4(const Args& a, const FrameView& F, float x, float y, float rs, int sub,
+                                            const uint32_t q[8], Keep keep, Within within, int32_t idx[4],
+                                            int32_t dist[4], int* n, bool* any) {
+    static_assert(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "a power of two below the wave");
+    uint32_t key[4] = {kAreaNone, kAreaNone, kAreaNone, kAreaNone};
+    int kid[4] = {-1, -1, -1, -1};
+    int count = 0, seen = 0;
+    CellRange r;
+    if (window_cells(a, x, y, rs, &r)) {
+        for (int ix = r.minX + sub; ix <= r.maxX; ix += G) {
+            const int j0 = F.cs[ix * kGridRows + r.minY], j1 = F.cs[ix * kGridRows + r.maxY + 1];
+            for (int j = j0; j < j1; ++j) {
+                int k = F.ci[j];
+                const float2 p = *reinterpret_cast<const float2*>(F.xy + 2LL * k);
+                if (!(fabsf(p.x - x) < rs && fabsf(p.y - y) < rs)) continue;
+                seen = 1;
+                if (!keep(k, octave_of(F, k))) continue;
+                const int d = hamming32(q, F.desc + 32LL * k);
+                if (!within(d)) continue;
+                ++count;
+                uint32_t kk = ((uint32_t)d << 22) | ((uint32_t)ix << 16) | (uint32_t)min(j - j0, 0xFFFF);
+                bool shift = false;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    shift = shift || kk < key[t];
+                    if (shift) {
+                        const uint32_t tk = key[t];
+                        const int ti = kid[t];
+                        key[t] = kk, kid[t] = k;
+                        kk = tk, k = ti;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) count += __shfl_xor(count, o), seen |= __shfl_xor(seen, o);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        uint32_t m = key[0];
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o));
+        const bool mine = m != kAreaNone && key[0] == m;
+        int mi = mine ? kid[0] : -1;
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) mi = max(mi, __shfl_xor(mi, o));
+        idx[t] = mi;
+        dist[t] = m != kAreaNone ? (int)(m >> 22) : 256;
+        if (mine) {
+            key[0] = key[1], key[1] = key[2], key[2] = key[3], key[3] = kAreaNone;
+            kid[0] = kid[1], kid[1] = kid[2], kid[2] = kid[3], kid[3] = -1;
+        }
+    }
+    *n = count;
+    *any = seen != 0;
 }
 
 // Candidate k at distance d into the four lowest (distance, window position) records: the candidates

@@ -453,3 +453,41 @@ def fuse_points(xy_un, kps, desc, K, pose, uright=None, bf=None, n=1000, seed=0,
             d[i] = np.packbits(b)
     out["desc"] = d
     return out
+
+
+def sim3_pose(sim3):
+    """The RELOC_POSE_DTYPE record the Sim3 searches take for Scw = (scale, rotation 3x3, translation 3):
+    Rcw = Scw.rotationMatrix(), tcw = Scw.translation() / Scw.scale(), Ow = Tcw.inverse().translation()
+    (ORBmatcher.cc:437-438), and (Rcw, tcw) in double for the generators."""
+    from . import RELOC_POSE_DTYPE
+    s, R, t = sim3
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    tcw = np.asarray(t, np.float64).reshape(3) / float(s)
+    p = np.zeros((), RELOC_POSE_DTYPE)
+    p["Rcw"], p["tcw"], p["Ow"] = R.reshape(9), tcw, -R.T @ tcw
+    return p, (R, tcw)
+
+
+def sim3_points(xy_un, kps, desc, K, sim3, n=1000, seed=0, th=8.0, bounds=(0.0, 640.0, 0.0, 480.0), pool=None,
+                contested=0.25, contested_pool=24, contested_flips=(0, 2, 5, 10, 20, 35), **shares):
+    """Synthetic map points for the Sim3 SearchByProjection overloads (a FUSE_POINT_DTYPE array): the
+    frame's keypoints back-projected through the inverse of the pose sim3_pose derives from Scw =
+    (scale, rotation, translation), as fuse_points does (whose shares of each rejection -- invalid,
+    behind, outside, too_near, too_far, bad_normal, empty, not_finite, level_offsets, over_top, flips,
+    z_range -- pass through `shares`; there is no chi-square share).  A share `contested` of the points
+    has none of those misses and aims at `contested_pool` keypoints only, at the keypoint's own level or
+    the one above, so that several points in a row want one keypoint, the later ones fall to their next
+    best and, with a wide window and limit, past the few candidates a kernel keeps.  The two kinds are
+    interleaved at random, so chains of contested points run through the whole list."""
+    rng = np.random.default_rng(seed + 7919)
+    _, pose = sim3_pose(sim3)
+    nc = int(round(n * contested))
+    common = dict(th=th, bounds=bounds, chi=0.0)
+    a = fuse_points(xy_un, kps, desc, K, pose, n=n - nc, seed=seed, pool=pool, **common, **shares)
+    clean = dict(invalid=0.0, behind=0.0, outside=0.0, too_near=0.0, too_far=0.0, bad_normal=0.0, empty=0.0,
+                 not_finite=0.0, over_top=0.0, level_offsets=(0, 0, 1), flips=contested_flips)
+    if "z_range" in shares:
+        clean["z_range"] = shares["z_range"]
+    b = fuse_points(xy_un, kps, desc, K, pose, n=nc, seed=seed + 1, pool=contested_pool, **common, **clean)
+    out = np.concatenate([a, b])
+    return out[rng.permutation(len(out))]
