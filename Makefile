@@ -12,7 +12,7 @@ all: $(LIB) oracle facade_test idl_test
 
 # one object per translation unit (each launcher sits beside its kernels: no relocatable device
 # code needed), so `make -j` compiles them in parallel
-LIBSRC := orb_pyramid.hip orb_fast.hip orb_octree.hip orb_orient.hip orb_knn2.hip orb_stereo.hip orb_frame.hip orb_io.hip orb_sbp.hip orb_track.hip orb_init.hip orb_bow.hip orb_tri.hip orb_reloc.hip orb_fuse.hip orb_sim3.hip orb_fisheye.hip orb_runtime.cpp orb_post.cpp orb_matchers.cpp
+LIBSRC := orb_pyramid.hip orb_fast.hip orb_octree.hip orb_orient.hip orb_knn2.hip orb_stereo.hip orb_frame.hip orb_io.hip orb_sbp.hip orb_track.hip orb_init.hip orb_bow.hip orb_bowkf.hip orb_tri.hip orb_reloc.hip orb_fuse.hip orb_sim3.hip orb_fisheye.hip orb_runtime.cpp orb_post.cpp orb_matchers.cpp
 OBJDIR := $(CSRC)/build
 LIBOBJ := $(patsubst %,$(OBJDIR)/%.o,$(LIBSRC))
 

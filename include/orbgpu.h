@@ -523,8 +523,9 @@ int orbgpu_download_bow_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int c
  * check_orientation == 0).  vMatchedPairs is the list of (k, match12[k]) over the non-negative
  * entries, k ascending (:1142-1150).  Errors as for orbgpu_download_bow_matches.
  * Not built: the two-camera SearchForTriangulation (mpCamera2 set: the Tll / Tlr / Trl / Trr
- * selection :1043-1077 and KannalaBrandt8::epipolarConstrain, which triangulates), SearchByBoW(KeyFrame*,
- * KeyFrame*) and the Sim3 searches (SearchBySim3, the Sim3 SearchByProjection overloads). */
+ * selection :1043-1077 and KannalaBrandt8::epipolarConstrain, which triangulates) and SearchBySim3, which
+ * has no caller.  SearchByBoW(KeyFrame*, KeyFrame*) is orbgpu_search_by_bow_kf_batch, the Sim3
+ * SearchByProjection overloads are orbgpu_sim3_search_by_projection_batch, both below. */
 typedef struct {
     uint8_t desc[32];  /* pKF2->mDescriptors.row(i) */
     float x, y;        /* pKF2->mvKeysUn[i].pt */
@@ -776,8 +777,8 @@ int orbgpu_download_fuse_matches(orbgpu_ctx* ctx, int pair, int32_t* best_idx, i
  * orbgpu_download_bow_matches.
  * orbgpu_sim3_replay_stats (measurement, tools/sim3_search_time.py): what the replay of pair `pair` did:
  * {points that reached it, passes, lanes found stale over all passes, windows walked again}.
- * Not built: the two-camera form (NLeft != -1), SearchByBoW(KeyFrame*, KeyFrame*), SearchBySim3, and the
- * Sim3Solver / Optimizer::OptimizeSim3 between the calls. */
+ * Not built: the two-camera form (NLeft != -1), SearchBySim3, and the Sim3Solver / Optimizer::OptimizeSim3
+ * between the calls. */
 #define ORBGPU_SIM3_PROJECT_DIV 0  /* :428, Pinhole::project */
 #define ORBGPU_SIM3_PROJECT_INVZ 1 /* :535, the invz form */
 #define ORBGPU_SIM3_SKIPPED 1
@@ -798,6 +799,75 @@ int orbgpu_download_sim3_matches(orbgpu_ctx* ctx, int pair, int32_t* match, int 
                                  int32_t* best_dist, uint8_t* code, int cap_points, int* n_kp, int* n_points,
                                  int* nmatches);
 int orbgpu_sim3_replay_stats(orbgpu_ctx* ctx, int pair, int32_t stats[4]);
+
+/* ---- ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) ----------
+ * The matcher LoopClosing::DetectCommonRegionsFromBoW runs on ORBmatcher(0.9, true) for the current keyframe
+ * against the candidate and each of its 5 covisibles, for up to 3 candidates (LoopClosing.cc:657-668): 6 to 18
+ * calls per new keyframe, whose matches feed the Sim3Solver: cpp/src/ORBmatcher.cc:766-906 with
+ * ComputeThreeMaxima :2061-2102, on pinhole keyframes (NLeft == -1 on both).  Pair p = keyframe 1, which is
+ * image frames[p] of the last orbgpu_run_batch (its descriptors and angles only: undistortion does not change
+ * mvKeysUn[i].angle, so orbgpu_undistort_grid_batch is not needed), against keyframe 2, given by the host as
+ * kf_pts [kf_offsets[p], kf_offsets[p + 1]); several pairs may name the same frame: one current keyframe against
+ * 6 to 18 keyframes is one call.  The vocabulary stays on the host: the node of each keypoint (mFeatVec) is an
+ * input on both sides.  It is the mirror of orbgpu_search_by_bow_batch, not the same search with the sides
+ * swapped: the batch image is the outer, sequential side, the taken bits live on the host-given side, both sides
+ * carry a map-point flag and the distance gate is strict.  All arithmetic is IEEE single, in the reference's
+ * order:
+ *   1. match12 has keyframe 1's N1 entries, all -1 (:778); vbMatched2 is all false (:779).
+ *   2. only the nodes present in both feature vectors are visited (:794-883); nodes do not interact; a node's
+ *      list holds keypoint indices in ascending order.
+ *   3. in a common node, for idx1 ascending (:798): a keypoint 1 without ORBGPU_BOWKF_HAS_POINT (vpMapPoints1
+ *      [idx1] && !isBad()) is skipped (:805-809).  The NLeft test at :801 cannot fire on pinhole keyframes; a host
+ *      that feeds a two-camera keyframe 1 would clear the flag of the keypoints that test skips.
+ *   4. for idx2 ascending (:817): a keypoint 2 that is taken (vbMatched2) or lacks ORBGPU_BOWKF_HAS_POINT is
+ *      passed over (:825-831): it is neither the best nor the second best.  Best and second best with strict <
+ *      from 256 / 256 (:837-846): an equal distance becomes the second best, never the best.
+ *   5. a match when bestDist1 < TH_LOW = 50 (:849: 49 passes, 50 fails; orbgpu_search_by_bow_batch has <=) and
+ *      (float)bestDist1 < nnratio * (float)bestDist2 (:851; a lone candidate has bestDist2 = 256): match12[idx1] =
+ *      bestIdx2, keypoint 2 is taken, nmatches++; with check_orientation, rot = angle1[idx1] - angle2[bestIdx2]
+ *      (+360 if negative), bin = round(rot * (1.0f / 30)) (30 -> 0), and idx1 enters that bin (:856-866).
+ *   6. ComputeThreeMaxima on the 30 bin sizes; every entry of a bin outside the three maxima is cleared and takes
+ *      one off nmatches (:885-903).  A cleared match does not free its keypoint 2 for anyone: nothing reads
+ *      vbMatched2 after the loop.
+ * Deviations: a negative node means "this keypoint is in no node"; an event whose bin falls outside [0, 30)
+ * (the reference asserts) counts in nmatches, enters no bin and cannot be rejected.  Parity with the reference
+ * is unpinned, as for the other matcher functions: the yardstick is the Python restatement in
+ * tests/test_search_by_bow_kf.py.
+ * f_nodes: [n_pairs][node_stride], the node of keypoint k of pair p's keyframe 1 at [p][k]; f_flags:
+ * [n_pairs][flag_stride] u8, bit 0 = ORBGPU_BOWKF_HAS_POINT of that keypoint, NULL: every keypoint 1 has a map
+ * point.  Host arrays are pageable and may be reused when the call returns.
+ * ORBGPU_ERR_INVALID: null context, n_pairs < 0 or above the context's image capacity, null arrays when n_pairs
+ * > 0, a frame outside the last batch, kf_offsets not ascending from a value >= 0, a stride below a frame's
+ * keypoint count, a nnratio that is not finite; n_pairs == 0 succeeds and leaves no pair to download.
+ * ORBGPU_ERR_CAPACITY when a side holds more than ORBGPU_BOW_MAX_POINTS keypoints (the context's keypoint
+ * capacity per image counts for keyframe 1).  Every status is decided before any launch.  The results live in
+ * buffers of their own: they outlive the other searches' calls and leave the other searches' results alone.
+ * orbgpu_download_bow_kf_matches, per keypoint k of keyframe 1 (each array may be NULL): match12[k] = the
+ * index, within the pair's keyframe points, that the reference leaves in vpMatches12[k] (vpMatches12[k] =
+ * vpMapPoints2[match12[k]]), -1 if none; code[k] = the decision it ended with, ORBGPU_BOWKF_*; best[2 k], best[2 k
+ * + 1] = bestDist1, bestDist2 of its walk (a side that found nothing holds 256; both are 0 for the codes
+ * NO_NODE, NODE_NOT_COMMON and NO_MAP_POINT, which never walk).  *n1 = N1; *nmatches = the reference's return
+ * value; rot_hist = the 30 bin sizes before the three-maxima rule (all 0 when check_orientation == 0).  Errors
+ * as for orbgpu_download_bow_matches.
+ * Not built: the two-camera form, and the union over a candidate's covisibles (LoopClosing.cc:670-687), which
+ * needs map-point identity: the host runs it over the downloaded rows. */
+typedef orbgpu_bow_point orbgpu_bowkf_point; /* desc, angle, node, flags of a keypoint of keyframe 2; 44 bytes */
+#define ORBGPU_BOWKF_HAS_POINT 1          /* vpMapPoints[i] && !isBad(): ORBGPU_BOW_HAS_POINT's bit */
+#define ORBGPU_BOWKF_NO_NODE 1            /* the keypoint's node is negative */
+#define ORBGPU_BOWKF_NODE_NOT_COMMON 2    /* keyframe 2 has no keypoint in its node */
+#define ORBGPU_BOWKF_NO_MAP_POINT 3       /* :805-809 */
+#define ORBGPU_BOWKF_NO_CANDIDATE 4       /* every keypoint 2 of the node taken or without a point: bestIdx2 == -1 */
+#define ORBGPU_BOWKF_NOT_BELOW_TH_LOW 5   /* :849 */
+#define ORBGPU_BOWKF_RATIO_FAILED 6       /* :851 */
+#define ORBGPU_BOWKF_MATCHED 7
+#define ORBGPU_BOWKF_ROTATION_REJECTED 8  /* matched, then cleared by the three-maxima rule */
+
+int orbgpu_search_by_bow_kf_batch(orbgpu_ctx* ctx, int n_pairs, const int32_t* frames,
+                                  const orbgpu_bowkf_point* kf_pts, const int32_t* kf_offsets,
+                                  const int32_t* f_nodes, int node_stride, const uint8_t* f_flags, int flag_stride,
+                                  float nnratio, int check_orientation, void* stream);
+int orbgpu_download_bow_kf_matches(orbgpu_ctx* ctx, int pair, int32_t* match12, uint8_t* code, int16_t* best,
+                                   int cap, int* n1, int* nmatches, int32_t rot_hist[30]);
 
 /* ---- wire formats ---------------------------------------------------------------------------
  * Ingest of side-by-side stereo Y8 frames (the headset's 2W x H AHardwareBuffer,

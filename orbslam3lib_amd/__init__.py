@@ -45,6 +45,12 @@ TRACK_RIG_DTYPE = np.dtype([("cam_left", "<f4", (8,)), ("Rrl", "<f4", (9,)), ("t
 BOW_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("angle", "<f4"), ("node", "<i4"), ("flags", "<i4")])
 BOW_HAS_POINT = 1  # ORBGPU_BOW_HAS_POINT
 BOW_MAX_POINTS = 8192  # ORBGPU_BOW_MAX_POINTS
+# orbgpu_bowkf_point: a keypoint of keyframe 2 for search_by_bow_kf, the same 44 bytes; ORBGPU_BOWKF_*: the
+# decision a keypoint of keyframe 1 ended with (ORBmatcher.cc:766-906)
+BOWKF_POINT_DTYPE = BOW_POINT_DTYPE
+BOWKF_HAS_POINT = 1  # ORBGPU_BOWKF_HAS_POINT
+(BOWKF_NO_NODE, BOWKF_NODE_NOT_COMMON, BOWKF_NO_MAP_POINT, BOWKF_NO_CANDIDATE, BOWKF_NOT_BELOW_TH_LOW,
+ BOWKF_RATIO_FAILED, BOWKF_MATCHED, BOWKF_ROTATION_REJECTED) = range(1, 9)
 # orbgpu_triang_point (56 B): a keypoint of keyframe 2 for search_for_triangulation; orbgpu_triang_pair
 # (44 B): the pair's F12 (row-major) and the epipole in keyframe 2
 TRIANG_POINT_DTYPE = np.dtype([("desc", "u1", (32,)), ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"),
@@ -99,6 +105,7 @@ EXPORTED = [
     "orbgpu_search_for_triangulation_batch", "orbgpu_download_triangulation_matches",
     "orbgpu_fuse_batch", "orbgpu_download_fuse_matches",
     "orbgpu_sim3_search_by_projection_batch", "orbgpu_download_sim3_matches", "orbgpu_sim3_replay_stats",
+    "orbgpu_search_by_bow_kf_batch", "orbgpu_download_bow_kf_matches",
 ]
 
 DEVICE_CURRENT = -1  # ORBGPU_DEVICE_CURRENT: the calling thread's current HIP device
@@ -918,6 +925,47 @@ class BatchExtractor:
         three-maxima rule) of pair `pair` of the last search_for_triangulation.  vMatchedPairs =
         [(k, match12[k]) for k in np.flatnonzero(match12 >= 0)]."""
         return self._download_matches(_lib.orbgpu_download_triangulation_matches, pair, cap)
+
+    def search_by_bow_kf(self, frames, kf_points, f_nodes, f_flags=None, nnratio=0.9, check_orientation=True,
+                         stream=None):
+        """ORBmatcher(nnratio, check_orientation).SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:766-906,
+        LoopClosing::DetectCommonRegionsFromBoW; pinhole keyframes) for pairs of a batch image of the last
+        run() (keyframe 1; undistort_grid() is not needed) and a keyframe the host gives (keyframe 2).  The
+        defaults are that caller's matcher, ORBmatcher matcherBoW(0.9, true) (LoopClosing.cc:591).  frames:
+        the batch image of each pair (one current keyframe usually serves all 6 to 18 pairs of a call);
+        kf_points: a list (one per pair) of BOWKF_POINT_DTYPE arrays, or (points, offsets) in the C ABI's
+        form; f_nodes: a list of int32 arrays (the node of each keypoint of keyframe 1, < 0: none) or one
+        2-D array [n_pairs, stride]; f_flags: the same shape in uint8 with BOWKF_HAS_POINT per keypoint of
+        keyframe 1, None: every keypoint has a map point."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        npairs = len(fr)
+        pts, off, _ = self._map_point_rows(kf_points, BOWKF_POINT_DTYPE, npairs)
+        nodes, _ = self._pad_rows(f_nodes, np.int32, -1)
+        if nodes.shape[0] != npairs:
+            raise ValueError("one row of nodes per pair")
+        flg, fstride = self._pad_rows(f_flags, np.uint8, 0)
+        if flg is not None and flg.shape[0] != npairs:
+            raise ValueError("one row of flags per pair")
+        _check(_lib.orbgpu_search_by_bow_kf_batch(
+            self.ctx.handle, npairs, _p(fr) if npairs else None, _p(pts) if npairs else None,
+            _p(off) if npairs else None, _p(nodes) if npairs else None, nodes.shape[1] if npairs else 0,
+            _p(flg) if flg is not None and npairs else None, fstride, C.c_float(nnratio), int(check_orientation),
+            C.c_void_p(stream) if stream else None))
+
+    def bow_kf_matches(self, pair, cap=65536):
+        """(match12 [N1] int32: for each keypoint of keyframe 1 the index, within the pair's keyframe points,
+        left in vpMatches12, -1 if none; nmatches; rot_hist [30] int32: the bin sizes before the
+        three-maxima rule; code [N1] uint8: BOWKF_*; best [N1, 2] int16: bestDist1, bestDist2 of the
+        keypoint's walk, 256 where a side found nothing, 0 where there was no walk) of pair `pair` of the
+        last search_by_bow_kf.  vpMatches12[k] = vpMapPoints2[match12[k]]."""
+        m = np.zeros(cap, np.int32)
+        code = np.zeros(cap, np.uint8)
+        best = np.zeros((cap, 2), np.int16)
+        h = np.zeros(30, np.int32)
+        n, nm = C.c_int(0), C.c_int(0)
+        _check(_lib.orbgpu_download_bow_kf_matches(self.ctx.handle, pair, _p(m), _p(code), _p(best), cap, C.byref(n),
+                                                   C.byref(nm), _p(h)))
+        return m[:n.value], nm.value, h, code[:n.value], best[:n.value]
 
     def reloc_by_projection(self, frames, kf_points, poses, K, kp_block=None, th=10.0, orb_dist=100,
                             check_orientation=True, stream=None):

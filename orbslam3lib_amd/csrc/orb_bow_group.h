@@ -1,8 +1,8 @@
-// orb_bow_group.h -- what the searches over vocabulary nodes share (orb_bow.hip: SearchByBoW,
-// orb_tri.hip: SearchForTriangulation): a pair's two sides ordered by (node, index) with their node
-// segment tables, the wave-wide minimum, and the rotation-histogram finish.  Args is the search's
-// argument struct (BowArgs / TriArgs, orb_kernels.h): the bodies read the fields both declare under
-// the same names.
+// orb_bow_group.h -- what the searches over vocabulary nodes share (orb_bow.hip: SearchByBoW(KeyFrame,
+// Frame), orb_tri.hip: SearchForTriangulation, orb_bowkf.hip: SearchByBoW(KeyFrame, KeyFrame)): a pair's
+// two sides ordered by (node, index) with their node segment tables, the segment lookup, the wave-wide
+// minimum, and the rotation-histogram finish.  Args is the search's argument struct (BowArgs / TriArgs /
+// BowKfArgs, orb_kernels.h): the bodies read the fields all declare under the same names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,6 +133,19 @@ inline hipError_t bow_group_lds(Kernel kernel, int max_side, size_t* lds) {
     return hipSuccess;
 }
 
+// The segment of `node` among a side's nseg segments (seg_node ascending), by the whole wave as in
+// k_bow_match: halve while the first node >= it lies in [lo, hi], then one probe per lane.  -1: the side
+// has no such node.
+__device__ inline int find_segment(const int32_t* seg_node, int nseg, int node, int lane) {
+    int lo = 0, hi = nseg;
+    while (hi - lo > 63) {
+        const int mid = (lo + hi) >> 1;
+        if (seg_node[mid] < node) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t hit = __ballot(lo + lane <= hi && lo + lane < nseg && seg_node[lo + lane] == node);
+    return hit ? lo + __builtin_ctzll(hit) : -1;
+}
+
 // Lane j's value of a wave-uniform j.
 __device__ inline uint32_t lane_value(uint32_t v, int j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, j); }
 
@@ -153,7 +166,9 @@ __device__ inline uint32_t wave_min(uint32_t v) {
 // One workgroup of 256 per pair, after the match kernel left match [pair][out_cap] and, beside each
 // match, the bin of the event that wrote it: the 30 bin sizes are counted from the stored bins (LDS
 // integer atomics: order-independent), then three_maxima_reject, the matches whose bin is rejected
-// are cleared, nmatches is what is left.  A row entry is written by at most one event.
+// are cleared, nmatches is what is left.  A row entry is written by at most one event.  (orb_bowkf.hip has
+// a finish of its own, which also codes the cleared entries: a hook here changed k_bow_finish's and
+// k_tri_finish's instruction order.)
 template <class Args>
 __device__ inline void bow_finish_body(const Args& a) {
     __shared__ uint32_t hist[kRotBins + 2];  // the bins, the rejected set, its size

@@ -140,10 +140,12 @@ struct orbgpu_ctx {
         relcand{bufs}, relblk{bufs}, relmatch{bufs}, relnm{bufs}, triin{bufs}, trikf{bufs}, trifn{bufs}, triflag{bufs},
         trigrp{bufs}, tridesc{bufs}, tripack{bufs}, trimatch{bufs}, trinm{bufs}, fusein{bufs}, fusept{bufs}, fusepose{bufs},
         fuseskip{bufs}, fuseout{bufs}, fusefirst{bufs}, fusenf{bufs}, sim3in{bufs}, sim3pt{bufs}, sim3pose{bufs}, sim3skip{bufs},
-        sim3blk{bufs}, sim3cand{bufs}, sim3out{bufs}, sim3match{bufs}, sim3nm{bufs};
+        sim3blk{bufs}, sim3cand{bufs}, sim3out{bufs}, sim3match{bufs}, sim3nm{bufs}, bkfin{bufs}, bkfpt{bufs}, bkffn{bufs},
+        bkfflag{bufs}, bkfgrp{bufs}, bkfdesc{bufs}, bkfpack{bufs}, bkfmatch{bufs}, bkfnm{bufs};
     float grid_bounds[4] = {0, 0, 0, 0}, grid_inv[2] = {0, 0};  // of the last undistort_grid
     // coverage of the last call of each ORBmatcher search (orb_matchers.cpp; init_cover: F1 of each pair)
-    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover, tri_cover, fuse_cover, sim3_cover;
+    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover, tri_cover, fuse_cover, sim3_cover,
+        bowkf_cover;
     std::vector<int32_t> fuse_off;  // the last orbgpu_fuse_batch: pair p's point rows are [fuse_off[p], fuse_off[p + 1])
     std::vector<int32_t> sim3_off;  // the same of the last orbgpu_sim3_search_by_projection_batch
     int soa_images = 0, soa_pairs = 0;  // coverage of the last orbgpu_pack_soa

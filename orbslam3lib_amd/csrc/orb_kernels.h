@@ -604,6 +604,45 @@ struct TriArgs {
 };
 hipError_t launch_tri_search(const TriArgs& a, int npairs, int max_side, hipStream_t st);
 
+// ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (orb_bowkf.hip),
+// pinhole keyframes.  Keyframe 1 is a batch image, keyframe 2 the host's points (BowPoint rows); the
+// grouping fields carry BowArgs' names (orb_bow_group.h reads them from either struct).
+enum BowKfCode : uint8_t {  // ORBGPU_BOWKF_*: what a keypoint of keyframe 1 ended with
+    kBowKfNoNode = 1, kBowKfNodeNotCommon, kBowKfNoMapPoint, kBowKfNoCandidate, kBowKfNotBelowThLow, kBowKfRatioFailed,
+    kBowKfMatched, kBowKfRotationRejected
+};
+struct BowKfArgs {
+    const int32_t* frames;    // [pair] the batch image that is keyframe 1
+    const BowPoint* kf_pts;   // all pairs' keyframe 2 points, pair p = [kf_off[p], kf_off[p + 1])
+    const int32_t* kf_off;    // [pair + 1], kf_off[0] == 0
+    const int32_t* f_nodes;   // [pair][out_cap] the node of each keypoint of keyframe 1, < 0: none
+    const uint8_t* f_flags;   // [pair][out_cap] bit 0: the keypoint of keyframe 1 has a map point; nullptr: all do
+    const void* kps;          // out_kps
+    const int32_t* out_n;
+    int out_cap;
+    const uint8_t* desc;      // out_desc
+    float nnratio;
+    int check_orientation;
+    // k_bowkf_group -> k_bowkf_match: each side's keypoints by (node, index) and its node segments
+    int32_t* kf_order;        // [kf point]
+    int32_t* kf_seg_node;     // [kf point]
+    int32_t* kf_seg_start;    // pair p at kf_off[p] + p, one entry more than its points
+    int32_t* f_order;         // [pair][out_cap]
+    int32_t* f_seg_node;      // [pair][out_cap]
+    int32_t* f_seg_start;     // [pair][out_cap + 1]
+    uint8_t* f_desc;          // [pair][out_cap][32] keyframe 1's descriptors in f_order's order
+    uint4* kf_desc;           // [kf point][2] keyframe 2's descriptors in kf_order's order
+    float2* kf_meta;          // [kf point] {angle, bits of flags} in kf_order's order
+    int32_t* nseg;            // [pair][2] segments of keyframe 2, of keyframe 1
+    int32_t* match;           // [pair][out_cap] match12
+    short2* best;             // [pair][out_cap] {bestDist1, bestDist2}
+    uint8_t* match_bin;       // [pair][out_cap] the bin of the event that wrote match
+    uint8_t* code;            // [pair][out_cap] BowKfCode
+    int32_t* nmatches;        // [pair]
+    int32_t* rot_hist;        // [pair][kRotBins] bin sizes before the three-maxima rule
+};
+hipError_t launch_bowkf_search(const BowKfArgs& a, int npairs, int max_side, hipStream_t st);
+
 // ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist)
 // (orb_reloc.hip).
 struct RelocPoint {  // orbgpu_reloc_point (60 B)

@@ -2,7 +2,8 @@
 // the device-resident results of a batch: the local-map search (orb_sbp.hip), the motion-model search
 // (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip), the
 // triangulation search (orb_tri.hip), the relocalisation search (orb_reloc.hip), the map-point fusion
-// (orb_fuse.hip) and the loop closer's Sim3 projection searches (orb_sim3.hip).  Every entry
+// (orb_fuse.hip), the loop closer's Sim3 projection searches (orb_sim3.hip) and its keyframe-to-keyframe
+// bag-of-words search (orb_bowkf.hip).  Every entry
 // point validates its own arguments and lays out its own buffers; what they share -- the offsets check, the padded row uploads, the common
 // argument fields, the launch path and the download -- is written once, below.
 #include <cmath>
@@ -703,6 +704,114 @@ int orbgpu_download_triangulation_matches(orbgpu_ctx* c, int pair, int32_t* matc
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
     return download_matches(c, c->tri_cover, pair, "bad pair", c->trimatch.as<int32_t>(), c->trinm.as<int32_t>(),
                             row_cap(c, false), match12, cap, n1, nmatches, rot_hist);
+}
+
+// ---- ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) on pinhole keyframes (orb_bowkf.hip) --------
+static_assert(sizeof(orbgpu_bowkf_point) == sizeof(BowPoint), "orbgpu_bowkf_point is orbgpu_bow_point");
+static_assert(ORBGPU_BOWKF_HAS_POINT == ORBGPU_BOW_HAS_POINT, "the two searches share the flag bit");
+static_assert(ORBGPU_BOWKF_NO_NODE == kBowKfNoNode && ORBGPU_BOWKF_NODE_NOT_COMMON == kBowKfNodeNotCommon &&
+                  ORBGPU_BOWKF_NO_MAP_POINT == kBowKfNoMapPoint && ORBGPU_BOWKF_NO_CANDIDATE == kBowKfNoCandidate &&
+                  ORBGPU_BOWKF_NOT_BELOW_TH_LOW == kBowKfNotBelowThLow && ORBGPU_BOWKF_RATIO_FAILED == kBowKfRatioFailed &&
+                  ORBGPU_BOWKF_MATCHED == kBowKfMatched && ORBGPU_BOWKF_ROTATION_REJECTED == kBowKfRotationRejected,
+              "the header states the decision codes");
+
+int orbgpu_search_by_bow_kf_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const orbgpu_bowkf_point* kf_pts,
+                                  const int32_t* kf_offsets, const int32_t* f_nodes, int node_stride,
+                                  const uint8_t* f_flags, int flag_stride, float nnratio, int check_orientation,
+                                  void* stream) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
+    if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
+    if (!std::isfinite(nnratio)) return fail(ORBGPU_ERR_INVALID, "nnratio not finite");
+    if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !f_nodes)) return fail(ORBGPU_ERR_INVALID, "null array");
+    for (int p = 0; p < n_pairs; ++p)
+        if (frames[p] < 0 || frames[p] >= c->last_images)
+            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_run_batch");
+    int max_kf, total;
+    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", &max_kf, &total)) return e;
+    if (n_pairs > 0 && (node_stride < 0 || (f_flags && flag_stride < 0)))
+        return fail(ORBGPU_ERR_INVALID, "negative stride");
+    if (n_pairs == 0) {
+        c->bowkf_cover.image.clear();
+        return ORBGPU_OK;
+    }
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nkf = (size_t)total;
+    const int max_side = std::max((int)cap, max_kf);
+    if (max_side > kBowMaxPoints)
+        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    // one row of nodes (and of flags) per pair: it must cover keyframe 1's keypoints
+    if (int e = rows_cover_counts(c, c->last_images, frames, 1, n_pairs, f_flags ? std::min(node_stride, flag_stride) : node_stride,
+                                  "node_stride or flag_stride below the frame's keypoint count"))
+        return e;
+    const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
+    HIP_TRY(hipSetDevice(c->device));
+    // bkfgrp: the BoW search's layout (kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order,
+    // f_seg_node [np * cap each], f_seg_start [np * (cap + 1)], nseg [2 np]); bkfpack: keyframe 2's packed rows,
+    // 32 B of descriptor and 8 B of {angle, flags} per point; bkfmatch: match [np * cap] int32, best [np * cap]
+    // of two int16, then the bins and the codes [np * cap] u8 each
+    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
+    if (c->bkfin.ensure(head.size() * 4 + 256) || c->bkfpt.ensure(nkf * sizeof(BowPoint) + 256) ||
+        c->bkffn.ensure(np * cap * 4 + 256) || (f_flags && c->bkfflag.ensure(np * cap + 256)) ||
+        c->bkfgrp.ensure(grp_words * 4 + 256) || c->bkfdesc.ensure(np * cap * 32 + 256) ||
+        c->bkfpack.ensure(nkf * 40 + 256) || c->bkfmatch.ensure(np * cap * 10 + 256) ||
+        c->bkfnm.ensure(np * (1 + kRotBins) * 4 + 256))
+        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (keyframe bag-of-words search)");
+    BowKfArgs a{};
+    a.frames = c->bkfin.as<int32_t>();
+    a.kf_off = a.frames + np;
+    a.kf_pts = c->bkfpt.as<BowPoint>();
+    a.f_nodes = c->bkffn.as<int32_t>();
+    a.f_flags = f_flags ? c->bkfflag.as<uint8_t>() : nullptr;
+    bind_frame(a, c);
+    a.nnratio = nnratio;
+    a.check_orientation = check_orientation != 0;
+    a.kf_order = c->bkfgrp.as<int32_t>();
+    a.kf_seg_node = a.kf_order + nkf;
+    a.kf_seg_start = a.kf_seg_node + nkf;
+    a.f_order = a.kf_seg_start + nkf + np;
+    a.f_seg_node = a.f_order + np * cap;
+    a.f_seg_start = a.f_seg_node + np * cap;
+    a.nseg = a.f_seg_start + np * (cap + 1);
+    a.f_desc = c->bkfdesc.as<uint8_t>();
+    a.kf_desc = c->bkfpack.as<uint4>();
+    a.kf_meta = reinterpret_cast<float2*>(a.kf_desc + 2 * nkf);
+    a.match = c->bkfmatch.as<int32_t>();
+    a.best = reinterpret_cast<short2*>(a.match + np * cap);
+    a.match_bin = reinterpret_cast<uint8_t*>(a.best + np * cap);
+    a.code = a.match_bin + np * cap;
+    a.nmatches = c->bkfnm.as<int32_t>();
+    a.rot_hist = a.nmatches + n_pairs;
+    const int r = run_search(
+        c, stream,
+        [&](hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(c->bkfin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
+            if (nkf)
+                HIP_TRY(hipMemcpyAsync(c->bkfpt.p, kf_pts + kf_offsets[0], nkf * sizeof(BowPoint), hipMemcpyHostToDevice, s));
+            if (f_flags)
+                if (int e = upload_rows(c->bkfflag.p, cap, f_flags, (size_t)flag_stride, std::min((size_t)flag_stride, cap), np, 0, s))
+                    return e;
+            return upload_rows(c->bkffn.p, cap * 4, f_nodes, (size_t)node_stride * 4,
+                               std::min((size_t)node_stride, cap) * 4, np, -1, s);
+        },
+        [&](hipStream_t s) { return launch_bowkf_search(a, n_pairs, max_side, s); });
+    if (r) return r;
+    set_cover(c->bowkf_cover, np, frames, 1, false);
+    return ORBGPU_OK;
+}
+
+int orbgpu_download_bow_kf_matches(orbgpu_ctx* c, int pair, int32_t* match12, uint8_t* code, int16_t* best, int cap,
+                                   int* n1, int* nmatches, int32_t rot_hist[30]) {
+    if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    int nk = 0;
+    int* pn = n1 ? n1 : &nk;
+    if (int r = download_matches(c, c->bowkf_cover, pair, "bad pair", c->bkfmatch.as<int32_t>(), c->bkfnm.as<int32_t>(),
+                                 row_cap(c, false), match12, cap, pn, nmatches, rot_hist))
+        return r;
+    // the two extra rows lie behind the match rows of all pairs: best, then (behind the bins) the codes
+    const size_t rows = c->bowkf_cover.image.size() * (size_t)c->plan.out_cap, row0 = (size_t)pair * c->plan.out_cap;
+    const int16_t* dbest = reinterpret_cast<const int16_t*>(c->bkfmatch.as<int32_t>() + rows);
+    if (best && *pn) D2H(best, dbest + 2 * row0, 4 * (size_t)*pn);
+    if (code && *pn) D2H(code, reinterpret_cast<const uint8_t*>(dbest + 2 * rows) + rows + row0, (size_t)*pn);
+    return ORBGPU_OK;
 }
 
 // ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (orb_reloc.hip) ----

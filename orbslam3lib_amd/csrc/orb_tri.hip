@@ -52,19 +52,6 @@ __global__ __launch_bounds__(kGroupThreads) void k_tri_group(TriArgs a) {
     });
 }
 
-// The segment of `node` among a side's nseg segments (seg_node ascending), by the whole wave as in
-// k_bow_match: halve while the first node >= it lies in [lo, hi], then one probe per lane.  -1: the side
-// has no such node.
-__device__ inline int find_segment(const int32_t* seg_node, int nseg, int node, int lane) {
-    int lo = 0, hi = nseg;
-    while (hi - lo > 63) {
-        const int mid = (lo + hi) >> 1;
-        if (seg_node[mid] < node) lo = mid + 1; else hi = mid;
-    }
-    const uint64_t hit = __ballot(lo + lane <= hi && lo + lane < nseg && seg_node[lo + lane] == node);
-    return hit ? lo + __builtin_ctzll(hit) : -1;
-}
-
 __device__ inline float lane_float(float v, int j) { return __uint_as_float(lane_value(__float_as_uint(v), j)); }
 
 __global__ __launch_bounds__(64) void k_tri_match(TriArgs a) {
