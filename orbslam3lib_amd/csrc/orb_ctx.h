@@ -13,6 +13,7 @@
 #include "../../include/orbgpu.h"
 #include "orb_geometry.h"
 #include "orb_kernels.h"
+#include "orb_layout.h"
 
 namespace orbgpu {
 
@@ -102,6 +103,27 @@ struct DiagKnobs {
 // What a matcher's last call left on the device: result row r is over batch image image[r] (two_cam: and image[r] + 1).
 struct MatchCover { std::vector<int32_t> image; bool two_cam = false; };
 
+enum Search { S_SBP, S_TRACK, S_INIT, S_BOW, S_RELOC, S_TRI, S_FUSE, S_SIM3, S_BOWKF, S_COUNT };
+
+// Where the results of a search's last call lie in its result buffer: exactly what its download reads
+// (nullptr: the search has no such slot).
+struct ResultSlots {
+    int32_t *match = nullptr, *nmatches = nullptr;      // [row][row_cap], [row] (fuse: first, nfused)
+    size_t row_cap = 0;                                 // entries of a match row
+    int32_t* hist = nullptr;                            // [row][kRotBins]; sim3: the replay's stats [row][kSim3Stats]
+    float* prev_out = nullptr;                          // init: [row][row_cap][2]
+    int32_t *best_idx = nullptr, *best_dist = nullptr;  // fuse, sim3: [point row]
+    uint8_t* code = nullptr;                            // fuse, sim3: [point row]; bowkf: [row][row_cap]
+    short2* best = nullptr;                             // bowkf: [row][row_cap] {bestDist1, bestDist2}
+};
+struct SearchResult {
+    DevBuf buf;  // never shared: one search's results outlive the other searches' calls
+    ResultSlots at;
+    MatchCover cover;
+    std::vector<int32_t> point_off;  // fuse, sim3: pair p's point rows are [point_off[p], point_off[p + 1])
+    SearchResult(std::vector<DevBuf*>& owner) : buf(owner) {}
+};
+
 // Device-to-host copy on the context's own stream, waited for before the call returns (the
 // callers ran ctx_sync first, so the stream is idle and the copy sees every result).  Never a
 // null-stream hipMemcpy: that would also order against other contexts' and torch's work.
@@ -132,22 +154,17 @@ struct orbgpu_ctx {
         outmono{bufs}, laps{bufs}, midx1{bufs}, mdist1{bufs}, midx2{bufs}, mdist2{bufs}, mnq{bufs}, mpart{bufs},
         scratch{bufs}, octdbg{bufs}, fastovf{bufs}, strow{bufs}, stidx{bufs}, stur{bufs}, stdepth{bufs},
         stsad{bufs}, gxy{bufs}, gcell{bufs}, gstart{bufs}, gidx{bufs}, sbs{bufs}, soa{bufs}, m16{bufs},
-        sbpmp{bufs}, sbpoff{bufs}, sbpcand{bufs}, sbpblk{bufs}, sbpmatch{bufs}, sbpnm{bufs}, sbplr{bufs},
-        fel2r{bufs}, fer2l{bufs}, fedepth{bufs}, fep3d{bufs}, fecnt{bufs}, trkpt{bufs}, trkoff{bufs}, trkframe{bufs},
-        trkcand{bufs}, trkblk{bufs}, trkmatch{bufs}, trknm{bufs}, trkmask{bufs}, trkside{bufs}, inipair{bufs}, iniprev{bufs},
-        inicand{bufs}, inil0{bufs}, inimatch{bufs}, inipout{bufs}, ininm{bufs}, bowin{bufs}, bowkf{bufs}, bowfn{bufs},
-        bowgrp{bufs}, bowdesc{bufs}, bowmatch{bufs}, bownm{bufs}, relin{bufs}, relpt{bufs}, relpose{bufs},
-        relcand{bufs}, relblk{bufs}, relmatch{bufs}, relnm{bufs}, triin{bufs}, trikf{bufs}, trifn{bufs}, triflag{bufs},
-        trigrp{bufs}, tridesc{bufs}, tripack{bufs}, trimatch{bufs}, trinm{bufs}, fusein{bufs}, fusept{bufs}, fusepose{bufs},
-        fuseskip{bufs}, fuseout{bufs}, fusefirst{bufs}, fusenf{bufs}, sim3in{bufs}, sim3pt{bufs}, sim3pose{bufs}, sim3skip{bufs},
-        sim3blk{bufs}, sim3cand{bufs}, sim3out{bufs}, sim3match{bufs}, sim3nm{bufs}, bkfin{bufs}, bkfpt{bufs}, bkffn{bufs},
-        bkfflag{bufs}, bkfgrp{bufs}, bkfdesc{bufs}, bkfpack{bufs}, bkfmatch{bufs}, bkfnm{bufs};
+        fel2r{bufs}, fer2l{bufs}, fedepth{bufs}, fep3d{bufs}, fecnt{bufs};
     float grid_bounds[4] = {0, 0, 0, 0}, grid_inv[2] = {0, 0};  // of the last undistort_grid
-    // coverage of the last call of each ORBmatcher search (orb_matchers.cpp; init_cover: F1 of each pair)
-    orbgpu::MatchCover sbp_cover, trk_cover, init_cover, bow_cover, reloc_cover, tri_cover, fuse_cover, sim3_cover,
-        bowkf_cover;
-    std::vector<int32_t> fuse_off;  // the last orbgpu_fuse_batch: pair p's point rows are [fuse_off[p], fuse_off[p + 1])
-    std::vector<int32_t> sim3_off;  // the same of the last orbgpu_sim3_search_by_projection_batch
+    // The ORBmatcher searches (orb_matchers.cpp).  `work` holds what dies with a call, for all nine: the
+    // uploaded inputs and the kernels' scratch, laid out anew by every call (orb_layout.h).  Sharing it rests
+    // on two facts: run_search waits for the search's stream before it returns, and a context is driven by
+    // one thread, so no kernel of an earlier search reads `work` when the next one lays it out.  An error
+    // path of run_search (a failed HIP call) returns before that wait; the next call's ensure may then free
+    // `work` under what was enqueued, and the hipFree in DevBuf::ensure waits for the device, as it always has.
+    DevBuf work{bufs};
+    // What a download reads, one record per search: results stay until that search runs again.
+    orbgpu::SearchResult res[orbgpu::S_COUNT] = {{bufs}, {bufs}, {bufs}, {bufs}, {bufs}, {bufs}, {bufs}, {bufs}, {bufs}};
     int soa_images = 0, soa_pairs = 0;  // coverage of the last orbgpu_pack_soa
     int grid_images = 0;   // images of the last orbgpu_undistort_grid_batch
     int stereo_pairs = 0;  // pairs of the last orbgpu_stereo_matches_batch

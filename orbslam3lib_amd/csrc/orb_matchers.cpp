@@ -3,10 +3,14 @@
 // (orb_track.hip), the initialisation search (orb_init.hip), the bag-of-words search (orb_bow.hip), the
 // triangulation search (orb_tri.hip), the relocalisation search (orb_reloc.hip), the map-point fusion
 // (orb_fuse.hip), the loop closer's Sim3 projection searches (orb_sim3.hip) and its keyframe-to-keyframe
-// bag-of-words search (orb_bowkf.hip).  Every entry
-// point validates its own arguments and lays out its own buffers; what they share -- the offsets check, the padded row uploads, the common
-// argument fields, the launch path and the download -- is written once, below.
+// bag-of-words search (orb_bowkf.hip).  Every entry point validates its own arguments, in its own order.
+// What dies with a call (uploaded inputs, the kernels' scratch) it lays out in the context's one workspace,
+// what its download reads in its own result buffer, each region named once (orb_layout.h); the download
+// reads the slots the call recorded.  What the searches share -- the offsets check, the padded row uploads,
+// the common argument fields, the node searches' grouping regions, the launch path and the download -- is
+// written once, below.
 #include <cmath>
+#include <type_traits>
 
 #include "orb_ctx.h"
 
@@ -46,8 +50,11 @@ int rows_cover_counts(orbgpu_ctx* c, int n_images, const int32_t* image, int ima
 
 // `rows` host rows of src_pitch bytes into device rows of dst_pitch bytes, `width` bytes of each;
 // fill_byte >= 0 fills the device rows first (what the copy leaves of a row reads as that byte).
-int upload_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows,
+// src == nullptr: an optional input the caller did not pass, nothing to do.
+int upload_rows(const void* dst_, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows,
                 int fill_byte, hipStream_t s) {
+    if (!src) return 0;
+    void* const dst = const_cast<void*>(dst_);  // an input region: the argument structs name those const
     if (fill_byte >= 0) HIP_TRY(hipMemsetAsync(dst, fill_byte, dst_pitch * rows, s));
     if (width) HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, width, rows, hipMemcpyHostToDevice, s));
     return 0;
@@ -86,30 +93,80 @@ void bind_scale(Args& a, const orbgpu_ctx* c) {
     a.nlevels = c->prm.nlevels;
 }
 
-// One search on the caller's (or the main) stream: what the batch left on the chunk streams
-// (keypoints, descriptors, grid, mvuRight) first, then upload(s), then launch(s).  The host inputs are
-// pageable: the call waits, so the caller may reuse them on return.
-template <class Upload, class Launch>
-int run_search(orbgpu_ctx* c, void* stream, Upload&& upload, Launch&& launch) {
+// Row r of a search's results = batch image images[r * step], or image r * step where there is no list.
+MatchCover cover_of(size_t rows, const int32_t* images, int step, bool two_cam) {
+    MatchCover cover;
+    cover.image.resize(rows);
+    for (size_t r = 0; r < rows; ++r) cover.image[r] = images ? images[r * step] : (int32_t)r * step;
+    cover.two_cam = two_cam;
+    return cover;
+}
+
+// A call over no pairs: the search has no row left.
+int no_results(SearchResult& res) {
+    res.cover.image.clear();
+    res.point_off.clear();
+    return ORBGPU_OK;
+}
+
+// The result slots every search has: its match rows, its counts and, where it has them (hist != nullptr),
+// hist_words words per row: the rotation histogram, or sim3's replay stats.
+ResultSlots add_match_rows(Layout& out, size_t rows, size_t row_cap, int32_t*& match, int32_t*& nmatches, int32_t** hist,
+                           size_t hist_words) {
+    ResultSlots rs;
+    rs.row_cap = row_cap;
+    rs.match = match = out.add<int32_t>(rows * row_cap);
+    rs.nmatches = nmatches = out.add<int32_t>(rows);
+    if (hist) rs.hist = *hist = out.add<int32_t>(rows * hist_words);
+    return rs;
+}
+
+// Host to device into an input region: the argument structs name those const (the kernels only read them).
+int h2d(const void* dst, const void* src, size_t bytes, hipStream_t s) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+// One search.  fill(ws, out, rs) names every region of the workspace and of the search's result buffer once,
+// as `field = ws.add<T>(n)`, and notes in rs the result slots the download reads.  It runs twice with the same
+// counts: over two empty layouts, for the sizes the buffers must hold, and, once they hold them, over the
+// buffers, for the addresses.  Then, on the caller's (or the main) stream: what the batch left on the chunk
+// streams (keypoints, descriptors, grid, mvuRight) first, then upload(s), then launch(s).  The host inputs
+// are pageable: the call waits, so the caller may reuse them on return -- and the workspace is free for the
+// next search.  Last, the search's record says where its results lie and what they cover.
+template <class Fill, class Upload, class Launch>
+int run_search(orbgpu_ctx* c, void* stream, SearchResult& res, const char* search, MatchCover cover, Fill&& fill,
+               Upload&& upload, Launch&& launch) {
+    ResultSlots rs;
+    Layout ws, out;
+    fill(ws, out, rs);
+    if (out.bytes > res.buf.bytes) no_results(res);  // the rows of the last call go with the buffer they lie in
+    if (c->work.ensure(ws.bytes) || res.buf.ensure(out.bytes))
+        return fail(ORBGPU_ERR_HIP, std::string("hipMalloc failed (") + search + ")");
+    ws = Layout{(uintptr_t)c->work.p};
+    out = Layout{(uintptr_t)res.buf.p};
+    fill(ws, out, rs);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (int r = join_all(c, s)) return r;
     if (int r = upload(s)) return r;
     if (int r = timed(c, ST_SBP, s, [&] { return launch(s); })) return r;
     HIP_TRY(hipStreamSynchronize(s));
     c->need_fork = true;  // the next batch's chunk streams must not overwrite what this reads
+    res.at = rs;
+    res.cover = std::move(cover);
     return ORBGPU_OK;
 }
 
-// Result row `row` of the search `cover` records.  dmatch: [rows][row_cap] on the device; dnm:
-// nmatches [rows], then the rotation histograms [rows][kRotBins] (read only when rot_hist is set).
-int download_matches(orbgpu_ctx* c, const MatchCover& cover, int row, const char* bad_row, const int32_t* dmatch,
-                     const int32_t* dnm, size_t row_cap, int32_t* match, int cap, int* n_kp, int* nmatches,
-                     int32_t* rot_hist) {
+// Result row `row` of the search's last call: its match row, its count and (when rot_hist is set) its
+// rotation histogram, from the slots the call recorded.
+int download_matches(orbgpu_ctx* c, const SearchResult& res, int row, const char* bad_row, int32_t* match, int cap,
+                     int* n_kp, int* nmatches, int32_t* rot_hist) {
+    const MatchCover& cover = res.cover;
     if (row < 0 || (size_t)row >= cover.image.size()) return fail(ORBGPU_ERR_INVALID, bad_row);
     if (int e_ = ctx_sync(c)) return e_;  // (sets the device)
     int32_t nk[2] = {0, 0}, nm = 0;
     D2H(nk, c->outn.as<int32_t>() + cover.image[(size_t)row], cover.two_cam ? 8 : 4);
-    D2H(&nm, dnm + row, 4);
+    D2H(&nm, res.at.nmatches + row, 4);
     if (int e = count_status(nk[0])) return e;
     if (cover.two_cam)
         if (int e = count_status(nk[1])) return e;
@@ -117,17 +174,10 @@ int download_matches(orbgpu_ctx* c, const MatchCover& cover, int row, const char
     const int n = nk[0] + nk[1];  // two-camera frames: Nleft + Nright, the right ones from Nleft on
     if (n_kp) *n_kp = n;
     if (nmatches) *nmatches = nm;
-    if (rot_hist) D2H(rot_hist, dnm + cover.image.size() + (size_t)row * kRotBins, 4 * kRotBins);
+    if (rot_hist) D2H(rot_hist, res.at.hist + (size_t)row * kRotBins, 4 * kRotBins);
     if (n > cap) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small");
-    if (match && n) D2H(match, dmatch + (size_t)row * row_cap, 4 * (size_t)n);
+    if (match && n) D2H(match, res.at.match + (size_t)row * res.at.row_cap, 4 * (size_t)n);
     return ORBGPU_OK;
-}
-
-// Row r of `cover` = batch image images[r * step], or image r * step where there is no list.
-void set_cover(MatchCover& cover, size_t rows, const int32_t* images, int step, bool two_cam) {
-    cover.image.resize(rows);
-    for (size_t r = 0; r < rows; ++r) cover.image[r] = images ? images[r * step] : (int32_t)r * step;
-    cover.two_cam = two_cam;
 }
 
 size_t row_cap(const orbgpu_ctx* c, bool two_cam) { return (two_cam ? 2 : 1) * (size_t)c->plan.out_cap; }
@@ -152,27 +202,13 @@ int sbp_run(orbgpu_ctx* c, int n_frames, int image_step, int two_cam, int use_ur
     if (int e = check_offsets(mp_offsets, n_frames, false, "mp_offsets", &max_mps, &total)) return e;
     if (total > 0 && !mps) return fail(ORBGPU_ERR_INVALID, "null map points");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = (size_t)c->plan.out_cap, ncap = row_cap(c, two_cam);
-    if (c->sbpmp.ensure((size_t)total * sizeof(MapPointIn) + 256) ||
-        c->sbpoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
-        c->sbpcand.ensure((size_t)total * sizeof(SbpCand) + 256) ||
-        c->sbpmatch.ensure((size_t)n_frames * ncap * 4 + 256) || c->sbpnm.ensure((size_t)n_frames * 4 + 256) ||
-        (kp_block && c->sbpblk.ensure((size_t)n_frames * ncap + 256)) ||
-        ((l2r || r2l) && c->sbplr.ensure((size_t)n_frames * cap * 8 + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (projection search)");
-    int32_t* dl2r = c->sbplr.as<int32_t>();
-    int32_t* dr2l = dl2r ? dl2r + (size_t)n_frames * cap : nullptr;
+    const size_t cap = (size_t)c->plan.out_cap, ncap = row_cap(c, two_cam), nf = (size_t)n_frames;
+    SearchResult& res = c->res[S_SBP];
     SbpArgs a{};
-    a.mps = c->sbpmp.as<MapPointIn>();
-    a.mp_off = c->sbpoff.as<int32_t>();
-    a.cand = c->sbpcand.as<SbpCand>();
     bind_frame(a, c);
     bind_grid(a, c);
     bind_scale(a, c);
     a.uright = use_uright ? c->stur.as<float>() : nullptr;
-    a.kp_block = kp_block ? c->sbpblk.as<uint8_t>() : nullptr;
-    a.l2r = l2r ? dl2r : nullptr;
-    a.r2l = r2l ? dr2l : nullptr;
     a.two_cam = two_cam;
     a.image_step = image_step;
     a.img0 = 0;
@@ -181,27 +217,26 @@ int sbp_run(orbgpu_ctx* c, int n_frames, int image_step, int two_cam, int use_ur
     a.th_far = th_far;
     a.far_points = far_points != 0;
     a.factor = th != 1.0;  // bFactor (:48)
-    a.match = c->sbpmatch.as<int32_t>();
-    a.nmatches = c->sbpnm.as<int32_t>();
-    const int r = run_search(
-        c, stream,
+    return run_search(
+        c, stream, res, "projection search", cover_of(nf, nullptr, image_step, two_cam != 0),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            a.mps = ws.add<MapPointIn>((size_t)total);
+            a.mp_off = ws.add<int32_t>(nf + 1);
+            a.cand = ws.add<SbpCand>((size_t)total);
+            a.kp_block = kp_block ? ws.add<uint8_t>(nf * ncap) : nullptr;
+            a.l2r = l2r ? ws.add<int32_t>(nf * cap) : nullptr;
+            a.r2l = r2l ? ws.add<int32_t>(nf * cap) : nullptr;
+            rs = add_match_rows(out, nf, ncap, a.match, a.nmatches, nullptr, 0);
+        },
         [&](hipStream_t s) -> int {
-            if (total) HIP_TRY(hipMemcpyAsync(c->sbpmp.p, mps, (size_t)total * sizeof(MapPointIn), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->sbpoff.p, mp_offsets, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-            if (kp_block)
-                if (int e = upload_rows(c->sbpblk.p, ncap, kp_block, kp_stride, std::min((size_t)kp_stride, ncap), n_frames, 0, s))
-                    return e;
+            if (int e = h2d(a.mps, mps, (size_t)total * sizeof(MapPointIn), s)) return e;
+            if (int e = h2d(a.mp_off, mp_offsets, (nf + 1) * 4, s)) return e;
+            if (int e = upload_rows(a.kp_block, ncap, kp_block, kp_stride, std::min((size_t)kp_stride, ncap), nf, 0, s)) return e;
             const size_t lrw = std::min((size_t)lr_stride, cap) * 4;
-            if (l2r)
-                if (int e = upload_rows(dl2r, cap * 4, l2r, (size_t)lr_stride * 4, lrw, n_frames, 0xFF, s)) return e;
-            if (r2l)
-                if (int e = upload_rows(dr2l, cap * 4, r2l, (size_t)lr_stride * 4, lrw, n_frames, 0xFF, s)) return e;
-            return 0;
+            if (int e = upload_rows(a.l2r, cap * 4, l2r, (size_t)lr_stride * 4, lrw, nf, 0xFF, s)) return e;
+            return upload_rows(a.r2l, cap * 4, r2l, (size_t)lr_stride * 4, lrw, nf, 0xFF, s);
         },
         [&](hipStream_t s) { return launch_sbp(a, n_frames, max_mps, s); });
-    if (r) return r;
-    set_cover(c->sbp_cover, n_frames, nullptr, image_step, two_cam != 0);
-    return ORBGPU_OK;
 }
 
 // Shared by the pinhole entry point (K, rig == nullptr) and the two-camera one (rig, K == nullptr:
@@ -241,56 +276,42 @@ int track_run(orbgpu_ctx* c, int n_frames, int image_step, int use_uright, const
         T.pad[0] = T.pad[1] = T.pad[2] = 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t cap = row_cap(c, two_cam);
+    const size_t cap = row_cap(c, two_cam), nf = (size_t)n_frames;
     const size_t sides = two_cam ? 2 : 1;  // candidate records per point
-    if (c->trkpt.ensure((size_t)total * sizeof(LastPointIn) + 256) || c->trkoff.ensure((size_t)(n_frames + 1) * 4 + 256) ||
-        c->trkframe.ensure((size_t)n_frames * sizeof(TrackFrame) + 256) ||
-        c->trkcand.ensure(sides * total * sizeof(TrackCand) + 256) || c->trkmatch.ensure((size_t)n_frames * cap * 4 + 256) ||
-        c->trknm.ensure((size_t)n_frames * (1 + kRotBins) * 4 + 256) ||
-        (kp_block && c->trkblk.ensure((size_t)n_frames * cap + 256)) ||
-        (two_cam && (c->trkmask.ensure((size_t)n_frames * cap * 4 + 256) ||
-                     c->trkside.ensure((size_t)n_frames * 2 * (kRotBins + 1) * 4 + 256))))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (motion-model search)");
+    SearchResult& res = c->res[S_TRACK];
     TrackStereoArgs a{};
-    a.pts = c->trkpt.as<LastPointIn>();
-    a.pt_off = c->trkoff.as<int32_t>();
-    a.frames = c->trkframe.as<TrackFrame>();
-    a.cand = c->trkcand.as<TrackCand>();
     bind_frame(a, c);
     bind_grid(a, c);
     bind_scale(a, c);
     a.uright = use_uright ? c->stur.as<float>() : nullptr;
-    a.kp_block = kp_block ? c->trkblk.as<uint8_t>() : nullptr;
     a.image_step = image_step;
     for (int k = 0; k < 4; ++k) a.K[k] = K ? K[k] : 0.f;
     a.mbf = mbf;
     a.th = th;
     a.check_orientation = check_orientation != 0;
-    a.match = c->trkmatch.as<int32_t>();
-    a.nmatches = c->trknm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_frames;
-    if (two_cam) {
-        std::memcpy(&a.rig, rig, sizeof a.rig);
-        a.side_mask = c->trkmask.as<uint32_t>();
-        a.side_hist = c->trkside.as<int32_t>();
-    }
-    const int r = run_search(
-        c, stream,
+    if (two_cam) std::memcpy(&a.rig, rig, sizeof a.rig);
+    return run_search(
+        c, stream, res, "motion-model search", cover_of(nf, nullptr, image_step, two_cam),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            a.pts = ws.add<LastPointIn>((size_t)total);
+            a.pt_off = ws.add<int32_t>(nf + 1);
+            a.frames = ws.add<TrackFrame>(nf);
+            a.cand = ws.add<TrackCand>(sides * total);
+            a.kp_block = kp_block ? ws.add<uint8_t>(nf * cap) : nullptr;
+            a.side_mask = two_cam ? ws.add<uint32_t>(nf * cap) : nullptr;
+            a.side_hist = two_cam ? ws.add<int32_t>(nf * 2 * (kRotBins + 1)) : nullptr;
+            rs = add_match_rows(out, nf, cap, a.match, a.nmatches, &a.rot_hist, kRotBins);
+        },
         [&](hipStream_t s) -> int {
-            if (total) HIP_TRY(hipMemcpyAsync(c->trkpt.p, pts, (size_t)total * sizeof(LastPointIn), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->trkoff.p, pt_offsets, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->trkframe.p, frames.data(), (size_t)n_frames * sizeof(TrackFrame), hipMemcpyHostToDevice, s));
-            if (kp_block)
-                return upload_rows(c->trkblk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), n_frames, 0, s);
-            return 0;
+            if (int e = h2d(a.pts, pts, (size_t)total * sizeof(LastPointIn), s)) return e;
+            if (int e = h2d(a.pt_off, pt_offsets, (nf + 1) * 4, s)) return e;
+            if (int e = h2d(a.frames, frames.data(), nf * sizeof(TrackFrame), s)) return e;
+            return upload_rows(a.kp_block, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), nf, 0, s);
         },
         [&](hipStream_t s) {
             return two_cam ? launch_track_stereo(a, n_frames, max_pts, s)
                            : launch_track(static_cast<const TrackArgs&>(a), n_frames, max_pts, s);
         });
-    if (r) return r;
-    set_cover(c->trk_cover, n_frames, nullptr, image_step, two_cam);
-    return ORBGPU_OK;
 }
 
 // MapPoint::PredictScale before its clamps (MapPoint.cc:541): log(float) is the host libm's logf
@@ -364,21 +385,108 @@ int check_list_pairs(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const in
     return 0;
 }
 
-// The point side of a download (fuse, sim3): pair `pair`'s rows of the three arrays that lie one after the
-// other on the device, best_idx [rows], best_dist [rows], code [rows], after the keypoint side `r` has
-// written its count: both counts are out before either capacity is judged.
-int download_point_rows(orbgpu_ctx* c, const std::vector<int32_t>& off, int pair, int r, const int32_t* didx,
-                        int32_t* best_idx, int32_t* best_dist, uint8_t* code, int cap_points, int* n_points) {
-    const size_t rows = (size_t)off.back(), row0 = (size_t)off[(size_t)pair];
-    const int n = off[(size_t)pair + 1] - off[(size_t)pair];
+// What fuse and sim3 lay out alike in the workspace, into the fields FuseArgs and Sim3Args name alike: the
+// head (frames, lists [np each], out_off [np + 1], list_off), the points, the poses and the skip rows.
+template <class Args>
+void add_list_regions(Layout& ws, Args& a, const ListPairs& lp, size_t np, bool skip) {
+    a.frames = ws.add<int32_t>(lp.head.size());
+    a.lists = a.frames + np;
+    a.out_off = a.lists + np;
+    a.list_off = a.out_off + np + 1;
+    a.pts = ws.add<FusePoint>((size_t)lp.total_pts);
+    a.poses = ws.add<RelocPose>(np);
+    a.skip = skip ? ws.add<uint8_t>(np * lp.skip_pitch) : nullptr;
+    a.skip_stride = (int)lp.skip_pitch;
+}
+
+// Their uploads (pts: the caller's, from list_offsets[0] on).
+template <class Args>
+int upload_list_inputs(const Args& a, const ListPairs& lp, size_t np, const void* pts, const void* poses,
+                       const uint8_t* skip, int skip_stride, hipStream_t s) {
+    if (int e = h2d(a.frames, lp.head.data(), lp.head.size() * 4, s)) return e;
+    if (int e = h2d(a.pts, pts, (size_t)lp.total_pts * sizeof(FusePoint), s)) return e;
+    if (int e = h2d(a.poses, poses, np * sizeof(RelocPose), s)) return e;
+    return upload_rows(a.skip, lp.skip_pitch, skip, (size_t)skip_stride, (size_t)lp.max_pts, np, 0, s);
+}
+
+// Their result slots of the point side, one entry per output row of all pairs.
+template <class Args>
+void add_point_rows(Layout& out, ResultSlots& rs, Args& a, size_t rows) {
+    rs.best_idx = a.best_idx = out.add<int32_t>(rows);
+    rs.best_dist = a.best_dist = out.add<int32_t>(rows);
+    rs.code = a.code = out.add<uint8_t>(rows);
+}
+
+// The point side of a download (fuse, sim3): pair `pair`'s rows of best_idx, best_dist and code, after the
+// keypoint side `r` has written its count: both counts are out before either capacity is judged.
+int download_point_rows(orbgpu_ctx* c, const SearchResult& res, int pair, int r, int32_t* best_idx, int32_t* best_dist,
+                        uint8_t* code, int cap_points, int* n_points) {
+    const size_t row0 = (size_t)res.point_off[(size_t)pair];
+    const int n = res.point_off[(size_t)pair + 1] - res.point_off[(size_t)pair];
     if (n_points) *n_points = n;
     if (r && r != ORBGPU_ERR_CAPACITY) return r;
     if (n > cap_points) return fail(ORBGPU_ERR_CAPACITY, "caller capacity too small (points)");
     if (r) return r;
-    if (best_idx && n) D2H(best_idx, didx + row0, 4 * (size_t)n);
-    if (best_dist && n) D2H(best_dist, didx + rows + row0, 4 * (size_t)n);
-    if (code && n) D2H(code, reinterpret_cast<const uint8_t*>(didx + 2 * rows) + row0, (size_t)n);
+    if (best_idx && n) D2H(best_idx, res.at.best_idx + row0, 4 * (size_t)n);
+    if (best_dist && n) D2H(best_dist, res.at.best_dist + row0, 4 * (size_t)n);
+    if (code && n) D2H(code, res.at.code + row0, (size_t)n);
     return ORBGPU_OK;
+}
+
+// The three searches over vocabulary nodes (bow, tri, bowkf): np pairs of a batch image (up to cap keypoints)
+// and a keyframe of the host's points (nkf in all), and a head of head_bytes: frames [np], kf_off [np + 1],
+// then what a search appends of its own.
+struct NodeDims { size_t np, nkf, cap, head_bytes; };
+
+// What the three lay out alike in the workspace, into the fields BowArgs, TriArgs and BowKfArgs name alike:
+// the head, the keyframe points, the node rows, what the grouping kernel leaves for the match kernel
+// (orb_bow_group.h), and match_bin, which the match kernel writes and the finish kernel of the same call
+// reads: no download does, so it lies in the workspace.
+template <class Args>
+void add_node_regions(Layout& ws, Args& a, const NodeDims& d) {
+    a.frames = reinterpret_cast<const int32_t*>(ws.add<uint8_t>(d.head_bytes));
+    a.kf_off = a.frames + d.np;
+    a.kf_pts = ws.add<std::remove_pointer_t<decltype(a.kf_pts)>>(d.nkf);
+    a.f_nodes = ws.add<int32_t>(d.np * d.cap);
+    a.kf_order = ws.add<int32_t>(d.nkf);
+    a.kf_seg_node = ws.add<int32_t>(d.nkf);
+    a.kf_seg_start = ws.add<int32_t>(d.nkf + d.np);  // pair p at kf_off[p] + p
+    a.f_order = ws.add<int32_t>(d.np * d.cap);
+    a.f_seg_node = ws.add<int32_t>(d.np * d.cap);
+    a.f_seg_start = ws.add<int32_t>(d.np * (d.cap + 1));
+    a.nseg = ws.add<int32_t>(2 * d.np);
+    a.f_desc = ws.add<uint8_t>(d.np * d.cap * 32);
+    a.match_bin = ws.add<uint8_t>(d.np * d.cap);
+}
+
+// The uploads the three share: the head, the keyframe points (the caller's, from kf_offsets[0] on), the flag
+// rows filled with 0 (into d_flags; f_flags == nullptr: none) and the node rows filled with -1.
+template <class Args>
+int upload_node_inputs(const Args& a, const uint8_t* d_flags, const NodeDims& d, const void* head, const void* kf_pts,
+                       const int32_t* f_nodes, int node_stride, const uint8_t* f_flags, int flag_stride, hipStream_t s) {
+    if (int e = h2d(a.frames, head, d.head_bytes, s)) return e;
+    if (int e = h2d(a.kf_pts, kf_pts, d.nkf * sizeof *a.kf_pts, s)) return e;
+    if (int e = upload_rows(d_flags, d.cap, f_flags, (size_t)flag_stride, std::min((size_t)flag_stride, d.cap), d.np, 0, s)) return e;
+    return upload_rows(a.f_nodes, d.cap * 4, f_nodes, (size_t)node_stride * 4, std::min((size_t)node_stride, d.cap) * 4, d.np, -1, s);
+}
+
+// The checks the three make alike, in the order all three keep: every pair's image lies among the first
+// n_images of the batch (`where`: the message otherwise), the offsets ascend, no stride is negative.
+int check_node_pairs(int n_pairs, const int32_t* frames, int n_images, const char* where, const int32_t* kf_offsets,
+                     bool negative_stride, const char* stride_msg, int* max_kf, int* total) {
+    for (int p = 0; p < n_pairs; ++p)
+        if (frames[p] < 0 || frames[p] >= n_images) return fail(ORBGPU_ERR_INVALID, where);
+    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", max_kf, total)) return e;
+    if (n_pairs > 0 && negative_stride) return fail(ORBGPU_ERR_INVALID, stride_msg);
+    return 0;
+}
+
+// *max_side = the longest side the grouping kernel orders in LDS: the context's keypoint capacity, or a keyframe
+int check_max_side(const orbgpu_ctx* c, int max_kf, int* max_side) {
+    *max_side = std::max(c->plan.out_cap, max_kf);
+    if (*max_side > kBowMaxPoints)
+        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    return 0;
 }
 
 }  // namespace
@@ -406,8 +514,7 @@ int orbgpu_search_by_projection_stereo(orbgpu_ctx* c, int n_pairs, const orbgpu_
 int orbgpu_download_projection_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp,
                                        int* nmatches) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad frame");
-    return download_matches(c, c->sbp_cover, frame, "bad frame", c->sbpmatch.as<int32_t>(), c->sbpnm.as<int32_t>(),
-                            row_cap(c, c->sbp_cover.two_cam), match, cap, n_kp, nmatches, nullptr);
+    return download_matches(c, c->res[S_SBP], frame, "bad frame", match, cap, n_kp, nmatches, nullptr);
 }
 
 // ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (orb_track.hip) --------
@@ -433,8 +540,7 @@ int orbgpu_track_by_projection_stereo(orbgpu_ctx* c, int n_pairs, const orbgpu_l
 int orbgpu_download_track_matches(orbgpu_ctx* c, int frame, int32_t* match, int cap, int* n_kp, int* nmatches,
                                   int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad frame");
-    return download_matches(c, c->trk_cover, frame, "bad frame", c->trkmatch.as<int32_t>(), c->trknm.as<int32_t>(),
-                            row_cap(c, c->trk_cover.two_cam), match, cap, n_kp, nmatches, rot_hist);
+    return download_matches(c, c->res[S_TRACK], frame, "bad frame", match, cap, n_kp, nmatches, rot_hist);
 }
 
 // ---- ORBmatcher::SearchForInitialization (orb_init.hip) -----------------------------------------
@@ -450,66 +556,50 @@ int orbgpu_search_for_initialization_batch(orbgpu_ctx* c, int n_pairs, const int
             return fail(ORBGPU_ERR_INVALID, "images must lie in the last orbgpu_undistort_grid_batch");
     if (n_pairs > 0 && init_replay_lds_bytes(c->plan.out_cap) > 160 * 1024)
         return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if (n_pairs == 0) {
-        c->init_cover.image.clear();
-        return ORBGPU_OK;
-    }
+    SearchResult& res = c->res[S_INIT];
+    if (n_pairs == 0) return no_results(res);
     const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
     if (prev_matched)  // one row of pm_stride points per pair: it must cover F1's keypoints
         if (int e = rows_cover_counts(c, c->grid_images, image_pairs, 2, n_pairs, pm_stride,
                                       "pm_stride below F1's keypoint count"))
             return e;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->inipair.ensure(np * 12 + 256) || c->inicand.ensure(np * cap * sizeof(InitCand) + 256) ||
-        c->inimatch.ensure(np * cap * 4 + 256) || c->inipout.ensure(np * cap * 8 + 256) ||
-        c->ininm.ensure(np * (1 + kRotBins) * 4 + 256) || c->inil0.ensure(np * (cap + 4) * 48 + 256) ||
-        (prev_matched && c->iniprev.ensure(np * cap * 8 + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (initialization search)");
-    int32_t* dpairs = c->inipair.as<int32_t>();
     InitArgs a{};
-    a.pairs = dpairs;
-    a.prev = prev_matched ? c->iniprev.as<float>() : nullptr;
-    a.cand = c->inicand.as<InitCand>();
-    a.nsearch = dpairs + 2 * np;
-    a.l0_desc = c->inil0.as<uint8_t>();
-    a.l0_xy = reinterpret_cast<float*>(a.l0_desc + np * cap * 32);
-    a.l0_idx = reinterpret_cast<int32_t*>(a.l0_xy + np * cap * 2);
-    a.l0_pre = a.l0_idx + np * cap;
     bind_frame(a, c);
     bind_grid(a, c);
     a.window = (float)window_size;
     a.nnratio = nnratio;
     a.check_orientation = check_orientation != 0;
-    a.match12 = c->inimatch.as<int32_t>();
-    a.prev_out = c->inipout.as<float>();
-    a.nmatches = c->ininm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    const int r = run_search(
-        c, stream,
+    return run_search(
+        c, stream, res, "initialization search", cover_of(np, image_pairs, 2, false),  // the rows are over F1's keypoints
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            a.pairs = ws.add<int32_t>(2 * np);
+            a.nsearch = ws.add<int32_t>(np);
+            a.prev = prev_matched ? ws.add<float>(np * cap * 2) : nullptr;
+            a.cand = ws.add<InitCand>(np * cap);
+            a.l0_desc = ws.add<uint8_t>(np * cap * 32);
+            a.l0_xy = ws.add<float>(np * cap * 2);
+            a.l0_idx = ws.add<int32_t>(np * cap);
+            a.l0_pre = ws.add<int32_t>(np * (cap + 1));
+            rs = add_match_rows(out, np, cap, a.match12, a.nmatches, &a.rot_hist, kRotBins);
+            rs.prev_out = a.prev_out = out.add<float>(np * cap * 2);
+        },
         [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(dpairs, image_pairs, np * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(dpairs + 2 * np, 0, np * 4, s));  // the searched-keypoint counts
-            if (prev_matched)
-                return upload_rows(c->iniprev.p, cap * 8, prev_matched, (size_t)pm_stride * 8,
-                                   std::min((size_t)pm_stride, cap) * 8, np, -1, s);
-            return 0;
+            if (int e = h2d(a.pairs, image_pairs, np * 8, s)) return e;
+            HIP_TRY(hipMemsetAsync(a.nsearch, 0, np * 4, s));  // the searched-keypoint counts
+            return upload_rows(a.prev, cap * 8, prev_matched, (size_t)pm_stride * 8, std::min((size_t)pm_stride, cap) * 8, np, -1, s);
         },
         [&](hipStream_t s) { return launch_init_search(a, n_pairs, s); });
-    if (r) return r;
-    set_cover(c->init_cover, np, image_pairs, 2, false);  // the rows are over F1's keypoints
-    return ORBGPU_OK;
 }
 
 int orbgpu_download_initialization_matches(orbgpu_ctx* c, int pair, int32_t* match12, float* prev_matched, int cap,
                                            int* n1, int* nmatches, int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    const SearchResult& res = c->res[S_INIT];
     int nk = 0;
     int* pn = n1 ? n1 : &nk;
-    if (int r = download_matches(c, c->init_cover, pair, "bad pair", c->inimatch.as<int32_t>(), c->ininm.as<int32_t>(),
-                                 row_cap(c, false), match12, cap, pn, nmatches, rot_hist))
-        return r;
-    if (prev_matched && *pn)
-        D2H(prev_matched, c->inipout.as<float>() + 2 * (size_t)pair * c->plan.out_cap, 8 * (size_t)*pn);
+    if (int r = download_matches(c, res, pair, "bad pair", match12, cap, pn, nmatches, rot_hist)) return r;
+    if (prev_matched && *pn) D2H(prev_matched, res.at.prev_out + 2 * (size_t)pair * res.at.row_cap, 8 * (size_t)*pn);
     return ORBGPU_OK;
 }
 
@@ -523,74 +613,41 @@ int orbgpu_search_by_bow_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames
     if (!c) return fail(ORBGPU_ERR_INVALID, "null ctx");
     if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
     if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !f_nodes)) return fail(ORBGPU_ERR_INVALID, "null array");
-    for (int p = 0; p < n_pairs; ++p)
-        if (frames[p] < 0 || frames[p] >= c->last_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_run_batch");
-    int max_kf, total;
-    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", &max_kf, &total)) return e;
-    if (n_pairs > 0 && node_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative node_stride");
-    if (n_pairs == 0) {
-        c->bow_cover.image.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nkf = (size_t)total;
+    int max_kf, total, max_side;
+    if (int e = check_node_pairs(n_pairs, frames, c->last_images, "frames must lie in the last orbgpu_run_batch", kf_offsets,
+                                 node_stride < 0, "negative node_stride", &max_kf, &total))
+        return e;
+    SearchResult& res = c->res[S_BOW];
+    if (n_pairs == 0) return no_results(res);
     // one row of node_stride nodes per pair: it must cover the frame's keypoints
     if (int e = rows_cover_counts(c, c->last_images, frames, 1, n_pairs, node_stride,
                                   "node_stride below the frame's keypoint count"))
         return e;
-    const int max_side = std::max((int)cap, max_kf);
-    if (max_side > kBowMaxPoints)
-        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    if (int e = check_max_side(c, max_kf, &max_side)) return e;
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
     const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
+    const NodeDims d{np, (size_t)total, cap, head.size() * 4};
     HIP_TRY(hipSetDevice(c->device));
-    // bowgrp: kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order, f_seg_node [np * cap
-    // each], f_seg_start [np * (cap + 1)], nseg [2 np]
-    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
-    if (c->bowin.ensure(head.size() * 4 + 256) || c->bowkf.ensure(nkf * sizeof(BowPoint) + 256) ||
-        c->bowfn.ensure(np * cap * 4 + 256) || c->bowgrp.ensure(grp_words * 4 + 256) ||
-        c->bowdesc.ensure(np * cap * 32 + 256) || c->bowmatch.ensure(np * cap * 5 + 256) ||
-        c->bownm.ensure(np * (1 + kRotBins) * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (bag-of-words search)");
     BowArgs a{};
-    a.frames = c->bowin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.kf_pts = c->bowkf.as<BowPoint>();
-    a.f_nodes = c->bowfn.as<int32_t>();
     bind_frame(a, c);
     a.nnratio = nnratio;
     a.check_orientation = check_orientation != 0;
-    a.kf_order = c->bowgrp.as<int32_t>();
-    a.kf_seg_node = a.kf_order + nkf;
-    a.kf_seg_start = a.kf_seg_node + nkf;
-    a.f_order = a.kf_seg_start + nkf + np;
-    a.f_seg_node = a.f_order + np * cap;
-    a.f_seg_start = a.f_seg_node + np * cap;
-    a.nseg = a.f_seg_start + np * (cap + 1);
-    a.f_desc = c->bowdesc.as<uint8_t>();
-    a.match = c->bowmatch.as<int32_t>();
-    a.match_bin = reinterpret_cast<uint8_t*>(a.match + np * cap);
-    a.nmatches = c->bownm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    const int r = run_search(
-        c, stream,
-        [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->bowin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-            if (nkf)
-                HIP_TRY(hipMemcpyAsync(c->bowkf.p, kf_pts + kf_offsets[0], nkf * sizeof(BowPoint), hipMemcpyHostToDevice, s));
-            return upload_rows(c->bowfn.p, cap * 4, f_nodes, (size_t)node_stride * 4,
-                               std::min((size_t)node_stride, cap) * 4, np, -1, s);
+    return run_search(
+        c, stream, res, "bag-of-words search", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            add_node_regions(ws, a, d);
+            rs = add_match_rows(out, np, cap, a.match, a.nmatches, &a.rot_hist, kRotBins);
+        },
+        [&](hipStream_t s) {
+            return upload_node_inputs(a, nullptr, d, head.data(), kf_pts + kf_offsets[0], f_nodes, node_stride, nullptr, 0, s);
         },
         [&](hipStream_t s) { return launch_bow_search(a, n_pairs, max_side, s); });
-    if (r) return r;
-    set_cover(c->bow_cover, np, frames, 1, false);
-    return ORBGPU_OK;
 }
 
 int orbgpu_download_bow_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
                                 int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    return download_matches(c, c->bow_cover, pair, "bad pair", c->bowmatch.as<int32_t>(), c->bownm.as<int32_t>(),
-                            row_cap(c, false), match, cap, n_kp, nmatches, rot_hist);
+    return download_matches(c, c->res[S_BOW], pair, "bad pair", match, cap, n_kp, nmatches, rot_hist);
 }
 
 // ---- ORBmatcher::SearchForTriangulation(pKF1, pKF2, ...) on pinhole keyframes (orb_tri.hip) --------
@@ -607,21 +664,14 @@ int orbgpu_search_for_triangulation_batch(orbgpu_ctx* c, int n_pairs, const int3
     if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
     if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !pairs || !f_nodes))
         return fail(ORBGPU_ERR_INVALID, "null array");
-    for (int p = 0; p < n_pairs; ++p)
-        if (frames[p] < 0 || frames[p] >= c->grid_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_undistort_grid_batch");
-    int max_kf, total;
-    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", &max_kf, &total)) return e;
-    if (n_pairs > 0 && (node_stride < 0 || (f_flags && flag_stride < 0)))
-        return fail(ORBGPU_ERR_INVALID, "negative stride");
-    if (n_pairs == 0) {
-        c->tri_cover.image.clear();
-        return ORBGPU_OK;
-    }
+    int max_kf, total, max_side;
+    if (int e = check_node_pairs(n_pairs, frames, c->grid_images, "frames must lie in the last orbgpu_undistort_grid_batch",
+                                 kf_offsets, node_stride < 0 || (f_flags && flag_stride < 0), "negative stride", &max_kf, &total))
+        return e;
+    SearchResult& res = c->res[S_TRI];
+    if (n_pairs == 0) return no_results(res);
     const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nkf = (size_t)total;
-    const int max_side = std::max((int)cap, max_kf);
-    if (max_side > kBowMaxPoints)
-        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    if (int e = check_max_side(c, max_kf, &max_side)) return e;
     for (size_t i = 0; i < nkf; ++i)  // the level tables are indexed with it
         if (kf_pts[kf_offsets[0] + i].octave < 0 || kf_pts[kf_offsets[0] + i].octave >= c->prm.nlevels)
             return fail(ORBGPU_ERR_INVALID, "octave of a keyframe point outside [0, nlevels)");
@@ -629,7 +679,7 @@ int orbgpu_search_for_triangulation_batch(orbgpu_ctx* c, int n_pairs, const int3
     if (int e = rows_cover_counts(c, c->grid_images, frames, 1, n_pairs, f_flags ? std::min(node_stride, flag_stride) : node_stride,
                                   "node_stride or flag_stride below the frame's keypoint count"))
         return e;
-    // triin: frames [np], offsets [np + 1], the pairs, then (8-byte aligned) the two level tables
+    // the head: frames [np], offsets [np + 1], the pairs, then (8-byte aligned) the two level tables
     const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
     const size_t pairs_at = head.size() * 4, tab_at = (pairs_at + np * sizeof(TriPair) + 7) & ~(size_t)7;
     std::vector<uint8_t> in(tab_at + kMaxLevels * 12, 0);
@@ -641,69 +691,38 @@ int orbgpu_search_for_triangulation_batch(orbgpu_ctx* c, int n_pairs, const int3
         std::memcpy(in.data() + tab_at + 8 * (size_t)l, &epi, 8);
         std::memcpy(in.data() + tab_at + 8 * (size_t)kMaxLevels + 4 * (size_t)l, &disc, 4);
     }
+    const NodeDims d{np, nkf, cap, in.size()};
     HIP_TRY(hipSetDevice(c->device));
-    // trigrp: the BoW search's layout (kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order,
-    // f_seg_node [np * cap each], f_seg_start [np * (cap + 1)], nseg [2 np]); tripack: keyframe 2's packed
-    // rows, 32 B of descriptor and 16 B of {x, y, angle, octave and flags} per point
-    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
-    if (c->triin.ensure(in.size() + 256) || c->trikf.ensure(nkf * sizeof(TriPoint) + 256) ||
-        c->trifn.ensure(np * cap * 4 + 256) || (f_flags && c->triflag.ensure(np * cap + 256)) ||
-        c->trigrp.ensure(grp_words * 4 + 256) || c->tridesc.ensure(np * cap * 32 + 256) ||
-        c->tripack.ensure(nkf * 48 + 256) || c->trimatch.ensure(np * cap * 5 + 256) ||
-        c->trinm.ensure(np * (1 + kRotBins) * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (triangulation search)");
     TriArgs a{};
-    a.frames = c->triin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.pairs = reinterpret_cast<const TriPair*>(c->triin.as<uint8_t>() + pairs_at);
-    a.epi_th = reinterpret_cast<const double*>(c->triin.as<uint8_t>() + tab_at);
-    a.disc_th = reinterpret_cast<const float*>(a.epi_th + kMaxLevels);
-    a.kf_pts = c->trikf.as<TriPoint>();
-    a.f_nodes = c->trifn.as<int32_t>();
-    a.f_flags = f_flags ? c->triflag.as<uint8_t>() : nullptr;
     bind_frame(a, c);
     a.xy_un = c->gxy.as<float>();
     a.nlevels = c->prm.nlevels;
     a.only_stereo = only_stereo != 0;
     a.coarse = coarse != 0;
     a.check_orientation = check_orientation != 0;
-    a.kf_order = c->trigrp.as<int32_t>();
-    a.kf_seg_node = a.kf_order + nkf;
-    a.kf_seg_start = a.kf_seg_node + nkf;
-    a.f_order = a.kf_seg_start + nkf + np;
-    a.f_seg_node = a.f_order + np * cap;
-    a.f_seg_start = a.f_seg_node + np * cap;
-    a.nseg = a.f_seg_start + np * (cap + 1);
-    a.f_desc = c->tridesc.as<uint8_t>();
-    a.kf_desc = c->tripack.as<uint4>();
-    a.kf_meta = reinterpret_cast<float4*>(a.kf_desc + 2 * nkf);
-    a.match = c->trimatch.as<int32_t>();
-    a.match_bin = reinterpret_cast<uint8_t*>(a.match + np * cap);
-    a.nmatches = c->trinm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    const int r = run_search(
-        c, stream,
-        [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->triin.p, in.data(), in.size(), hipMemcpyHostToDevice, s));
-            if (nkf)
-                HIP_TRY(hipMemcpyAsync(c->trikf.p, kf_pts + kf_offsets[0], nkf * sizeof(TriPoint), hipMemcpyHostToDevice, s));
-            if (f_flags)
-                if (int e = upload_rows(c->triflag.p, cap, f_flags, (size_t)flag_stride, std::min((size_t)flag_stride, cap), np, 0, s))
-                    return e;
-            return upload_rows(c->trifn.p, cap * 4, f_nodes, (size_t)node_stride * 4,
-                               std::min((size_t)node_stride, cap) * 4, np, -1, s);
+    return run_search(
+        c, stream, res, "triangulation search", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            add_node_regions(ws, a, d);
+            const uint8_t* const dhead = reinterpret_cast<const uint8_t*>(a.frames);  // what the head appends
+            a.pairs = reinterpret_cast<const TriPair*>(dhead + pairs_at);
+            a.epi_th = reinterpret_cast<const double*>(dhead + tab_at);
+            a.disc_th = reinterpret_cast<const float*>(a.epi_th + kMaxLevels);
+            a.f_flags = f_flags ? ws.add<uint8_t>(np * cap) : nullptr;
+            a.kf_desc = ws.add<uint4>(2 * nkf);  // keyframe 2's packed rows: 32 B of descriptor
+            a.kf_meta = ws.add<float4>(nkf);     // and 16 B of {x, y, angle, octave and flags} per point
+            rs = add_match_rows(out, np, cap, a.match, a.nmatches, &a.rot_hist, kRotBins);
+        },
+        [&](hipStream_t s) {
+            return upload_node_inputs(a, a.f_flags, d, in.data(), kf_pts + kf_offsets[0], f_nodes, node_stride, f_flags, flag_stride, s);
         },
         [&](hipStream_t s) { return launch_tri_search(a, n_pairs, max_side, s); });
-    if (r) return r;
-    set_cover(c->tri_cover, np, frames, 1, false);
-    return ORBGPU_OK;
 }
 
 int orbgpu_download_triangulation_matches(orbgpu_ctx* c, int pair, int32_t* match12, int cap, int* n1, int* nmatches,
                                           int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    return download_matches(c, c->tri_cover, pair, "bad pair", c->trimatch.as<int32_t>(), c->trinm.as<int32_t>(),
-                            row_cap(c, false), match12, cap, n1, nmatches, rot_hist);
+    return download_matches(c, c->res[S_TRI], pair, "bad pair", match12, cap, n1, nmatches, rot_hist);
 }
 
 // ---- ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) on pinhole keyframes (orb_bowkf.hip) --------
@@ -723,94 +742,52 @@ int orbgpu_search_by_bow_kf_batch(orbgpu_ctx* c, int n_pairs, const int32_t* fra
     if (n_pairs < 0 || n_pairs > c->max_images) return fail(ORBGPU_ERR_INVALID, "bad pair count");
     if (!std::isfinite(nnratio)) return fail(ORBGPU_ERR_INVALID, "nnratio not finite");
     if (n_pairs > 0 && (!frames || !kf_pts || !kf_offsets || !f_nodes)) return fail(ORBGPU_ERR_INVALID, "null array");
-    for (int p = 0; p < n_pairs; ++p)
-        if (frames[p] < 0 || frames[p] >= c->last_images)
-            return fail(ORBGPU_ERR_INVALID, "frames must lie in the last orbgpu_run_batch");
-    int max_kf, total;
-    if (int e = check_offsets(kf_offsets, n_pairs, true, "kf_offsets", &max_kf, &total)) return e;
-    if (n_pairs > 0 && (node_stride < 0 || (f_flags && flag_stride < 0)))
-        return fail(ORBGPU_ERR_INVALID, "negative stride");
-    if (n_pairs == 0) {
-        c->bowkf_cover.image.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, nkf = (size_t)total;
-    const int max_side = std::max((int)cap, max_kf);
-    if (max_side > kBowMaxPoints)
-        return fail(ORBGPU_ERR_CAPACITY, "more keypoints on a side than the grouping kernel orders (ORBGPU_BOW_MAX_POINTS)");
+    int max_kf, total, max_side;
+    if (int e = check_node_pairs(n_pairs, frames, c->last_images, "frames must lie in the last orbgpu_run_batch", kf_offsets,
+                                 node_stride < 0 || (f_flags && flag_stride < 0), "negative stride", &max_kf, &total))
+        return e;
+    SearchResult& res = c->res[S_BOWKF];
+    if (n_pairs == 0) return no_results(res);
+    if (int e = check_max_side(c, max_kf, &max_side)) return e;
     // one row of nodes (and of flags) per pair: it must cover keyframe 1's keypoints
     if (int e = rows_cover_counts(c, c->last_images, frames, 1, n_pairs, f_flags ? std::min(node_stride, flag_stride) : node_stride,
                                   "node_stride or flag_stride below the frame's keypoint count"))
         return e;
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
     const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
+    const NodeDims d{np, (size_t)total, cap, head.size() * 4};
     HIP_TRY(hipSetDevice(c->device));
-    // bkfgrp: the BoW search's layout (kf_order, kf_seg_node [nkf each], kf_seg_start [nkf + np], f_order,
-    // f_seg_node [np * cap each], f_seg_start [np * (cap + 1)], nseg [2 np]); bkfpack: keyframe 2's packed rows,
-    // 32 B of descriptor and 8 B of {angle, flags} per point; bkfmatch: match [np * cap] int32, best [np * cap]
-    // of two int16, then the bins and the codes [np * cap] u8 each
-    const size_t grp_words = 3 * nkf + np + 3 * np * cap + np + 2 * np;
-    if (c->bkfin.ensure(head.size() * 4 + 256) || c->bkfpt.ensure(nkf * sizeof(BowPoint) + 256) ||
-        c->bkffn.ensure(np * cap * 4 + 256) || (f_flags && c->bkfflag.ensure(np * cap + 256)) ||
-        c->bkfgrp.ensure(grp_words * 4 + 256) || c->bkfdesc.ensure(np * cap * 32 + 256) ||
-        c->bkfpack.ensure(nkf * 40 + 256) || c->bkfmatch.ensure(np * cap * 10 + 256) ||
-        c->bkfnm.ensure(np * (1 + kRotBins) * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (keyframe bag-of-words search)");
     BowKfArgs a{};
-    a.frames = c->bkfin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.kf_pts = c->bkfpt.as<BowPoint>();
-    a.f_nodes = c->bkffn.as<int32_t>();
-    a.f_flags = f_flags ? c->bkfflag.as<uint8_t>() : nullptr;
     bind_frame(a, c);
     a.nnratio = nnratio;
     a.check_orientation = check_orientation != 0;
-    a.kf_order = c->bkfgrp.as<int32_t>();
-    a.kf_seg_node = a.kf_order + nkf;
-    a.kf_seg_start = a.kf_seg_node + nkf;
-    a.f_order = a.kf_seg_start + nkf + np;
-    a.f_seg_node = a.f_order + np * cap;
-    a.f_seg_start = a.f_seg_node + np * cap;
-    a.nseg = a.f_seg_start + np * (cap + 1);
-    a.f_desc = c->bkfdesc.as<uint8_t>();
-    a.kf_desc = c->bkfpack.as<uint4>();
-    a.kf_meta = reinterpret_cast<float2*>(a.kf_desc + 2 * nkf);
-    a.match = c->bkfmatch.as<int32_t>();
-    a.best = reinterpret_cast<short2*>(a.match + np * cap);
-    a.match_bin = reinterpret_cast<uint8_t*>(a.best + np * cap);
-    a.code = a.match_bin + np * cap;
-    a.nmatches = c->bkfnm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    const int r = run_search(
-        c, stream,
-        [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->bkfin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-            if (nkf)
-                HIP_TRY(hipMemcpyAsync(c->bkfpt.p, kf_pts + kf_offsets[0], nkf * sizeof(BowPoint), hipMemcpyHostToDevice, s));
-            if (f_flags)
-                if (int e = upload_rows(c->bkfflag.p, cap, f_flags, (size_t)flag_stride, std::min((size_t)flag_stride, cap), np, 0, s))
-                    return e;
-            return upload_rows(c->bkffn.p, cap * 4, f_nodes, (size_t)node_stride * 4,
-                               std::min((size_t)node_stride, cap) * 4, np, -1, s);
+    return run_search(
+        c, stream, res, "keyframe bag-of-words search", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            add_node_regions(ws, a, d);
+            a.f_flags = f_flags ? ws.add<uint8_t>(np * cap) : nullptr;
+            a.kf_desc = ws.add<uint4>(2 * d.nkf);  // keyframe 2's packed rows: 32 B of descriptor
+            a.kf_meta = ws.add<float2>(d.nkf);     // and 8 B of {angle, flags} per point
+            rs = add_match_rows(out, np, cap, a.match, a.nmatches, &a.rot_hist, kRotBins);
+            rs.best = a.best = out.add<short2>(np * cap);
+            rs.code = a.code = out.add<uint8_t>(np * cap);
+        },
+        [&](hipStream_t s) {
+            return upload_node_inputs(a, a.f_flags, d, head.data(), kf_pts + kf_offsets[0], f_nodes, node_stride, f_flags, flag_stride, s);
         },
         [&](hipStream_t s) { return launch_bowkf_search(a, n_pairs, max_side, s); });
-    if (r) return r;
-    set_cover(c->bowkf_cover, np, frames, 1, false);
-    return ORBGPU_OK;
 }
 
 int orbgpu_download_bow_kf_matches(orbgpu_ctx* c, int pair, int32_t* match12, uint8_t* code, int16_t* best, int cap,
                                    int* n1, int* nmatches, int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    const SearchResult& res = c->res[S_BOWKF];
     int nk = 0;
     int* pn = n1 ? n1 : &nk;
-    if (int r = download_matches(c, c->bowkf_cover, pair, "bad pair", c->bkfmatch.as<int32_t>(), c->bkfnm.as<int32_t>(),
-                                 row_cap(c, false), match12, cap, pn, nmatches, rot_hist))
-        return r;
-    // the two extra rows lie behind the match rows of all pairs: best, then (behind the bins) the codes
-    const size_t rows = c->bowkf_cover.image.size() * (size_t)c->plan.out_cap, row0 = (size_t)pair * c->plan.out_cap;
-    const int16_t* dbest = reinterpret_cast<const int16_t*>(c->bkfmatch.as<int32_t>() + rows);
-    if (best && *pn) D2H(best, dbest + 2 * row0, 4 * (size_t)*pn);
-    if (code && *pn) D2H(code, reinterpret_cast<const uint8_t*>(dbest + 2 * rows) + rows + row0, (size_t)*pn);
+    if (int r = download_matches(c, res, pair, "bad pair", match12, cap, pn, nmatches, rot_hist)) return r;
+    const size_t row0 = (size_t)pair * res.at.row_cap;
+    if (best && *pn) D2H(best, res.at.best + row0, 4 * (size_t)*pn);
+    if (code && *pn) D2H(code, res.at.code + row0, (size_t)*pn);
     return ORBGPU_OK;
 }
 
@@ -844,10 +821,8 @@ int orbgpu_reloc_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int32_t* 
     if (n_pairs > 0 && kp_block && kp_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative kp_stride");
     if (n_pairs > 0 && reloc_resolve_lds_bytes(c->plan.out_cap) > 160 * 1024)
         return fail(ORBGPU_ERR_CAPACITY, "keypoint capacity above the matcher's LDS budget");
-    if (n_pairs == 0) {
-        c->reloc_cover.image.clear();
-        return ORBGPU_OK;
-    }
+    SearchResult& res = c->res[S_RELOC];
+    if (n_pairs == 0) return no_results(res);
     const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, total = (size_t)total_pts;
     if (kp_block)  // one row of kp_stride flags per pair: it must cover the frame's keypoints
         if (int e = rows_cover_counts(c, c->grid_images, frames, 1, n_pairs, kp_stride,
@@ -855,50 +830,39 @@ int orbgpu_reloc_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int32_t* 
             return e;
     const std::vector<int32_t> head = frames_and_offsets(frames, kf_offsets, np);
     HIP_TRY(hipSetDevice(c->device));
-    if (c->relin.ensure(head.size() * 4 + 256) || c->relpt.ensure(total * sizeof(RelocPoint) + 256) ||
-        c->relpose.ensure(np * sizeof(RelocPose) + 256) || c->relcand.ensure(total * sizeof(RelocCand) + 256) ||
-        c->relmatch.ensure(np * cap * 4 + 256) || c->relnm.ensure(np * (1 + kRotBins) * 4 + 256) ||
-        (kp_block && c->relblk.ensure(np * cap + 256)))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (relocalisation search)");
     RelocArgs a{};
-    a.frames = c->relin.as<int32_t>();
-    a.kf_off = a.frames + np;
-    a.pts = c->relpt.as<RelocPoint>();
-    a.poses = c->relpose.as<RelocPose>();
-    a.cand = c->relcand.as<RelocCand>();
     bind_frame(a, c);
     bind_grid(a, c);
     bind_scale(a, c);
-    a.kp_block = kp_block ? c->relblk.as<uint8_t>() : nullptr;
     predict_scale_table(c->prm.scale_factor, c->prm.nlevels, a.level_step);  // Frame.cc:132 + MapPoint.cc:541
     for (int k = 0; k < 4; ++k) a.K[k] = K[k];
     a.th = th;
     a.orb_dist = orb_dist;
     a.check_orientation = check_orientation != 0;
-    a.match = c->relmatch.as<int32_t>();
-    a.nmatches = c->relnm.as<int32_t>();
-    a.rot_hist = a.nmatches + n_pairs;
-    const int r = run_search(
-        c, stream,
+    return run_search(
+        c, stream, res, "relocalisation search", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            a.frames = ws.add<int32_t>(head.size());
+            a.kf_off = a.frames + np;
+            a.pts = ws.add<RelocPoint>(total);
+            a.poses = ws.add<RelocPose>(np);
+            a.cand = ws.add<RelocCand>(total);
+            a.kp_block = kp_block ? ws.add<uint8_t>(np * cap) : nullptr;
+            rs = add_match_rows(out, np, cap, a.match, a.nmatches, &a.rot_hist, kRotBins);
+        },
         [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->relin.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-            if (total)
-                HIP_TRY(hipMemcpyAsync(c->relpt.p, pts + kf_offsets[0], total * sizeof(RelocPoint), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->relpose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
-            if (kp_block) return upload_rows(c->relblk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), np, 0, s);
-            return 0;
+            if (int e = h2d(a.frames, head.data(), head.size() * 4, s)) return e;
+            if (int e = h2d(a.pts, pts ? pts + kf_offsets[0] : nullptr, total * sizeof(RelocPoint), s)) return e;
+            if (int e = h2d(a.poses, poses, np * sizeof(RelocPose), s)) return e;
+            return upload_rows(a.kp_block, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), np, 0, s);
         },
         [&](hipStream_t s) { return launch_reloc(a, n_pairs, max_pts, s); });
-    if (r) return r;
-    set_cover(c->reloc_cover, np, frames, 1, false);
-    return ORBGPU_OK;
 }
 
 int orbgpu_download_reloc_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap, int* n_kp, int* nmatches,
                                   int32_t rot_hist[30]) {
     if (!c) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    return download_matches(c, c->reloc_cover, pair, "bad pair", c->relmatch.as<int32_t>(), c->relnm.as<int32_t>(),
-                            row_cap(c, false), match, cap, n_kp, nmatches, rot_hist);
+    return download_matches(c, c->res[S_RELOC], pair, "bad pair", match, cap, n_kp, nmatches, rot_hist);
 }
 
 // ---- ORBmatcher::Fuse(pKF, vpMapPoints, th) and its Sim3 overload on pinhole keyframes (orb_fuse.hip) ----
@@ -927,29 +891,11 @@ int orbgpu_fuse_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const i
                                      return 0;
                                  }))
         return e;
-    if (n_pairs == 0) {
-        c->fuse_cover.image.clear();
-        c->fuse_off.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, total = (size_t)lp.total_pts;
-    const std::vector<int32_t>& head = lp.head;
-    const size_t rows = lp.rows, skip_pitch = lp.skip_pitch;
-    const int max_pts = lp.max_pts;
+    SearchResult& res = c->res[S_FUSE];
+    if (n_pairs == 0) return no_results(res);
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->fusein.ensure(head.size() * 4 + 256) || c->fusept.ensure(total * sizeof(FusePoint) + 256) ||
-        c->fusepose.ensure(np * sizeof(RelocPose) + 256) || (skip && c->fuseskip.ensure(np * skip_pitch + 256)) ||
-        c->fuseout.ensure(rows * 9 + 256) || c->fusefirst.ensure(np * cap * 4 + 256) || c->fusenf.ensure(np * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (fuse)");
     FuseArgs a{};
-    a.frames = c->fusein.as<int32_t>();
-    a.lists = a.frames + np;
-    a.out_off = a.lists + np;
-    a.list_off = a.out_off + np + 1;
-    a.pts = c->fusept.as<FusePoint>();
-    a.poses = c->fusepose.as<RelocPose>();
-    a.skip = skip ? c->fuseskip.as<uint8_t>() : nullptr;
-    a.skip_stride = (int)skip_pitch;
     bind_frame(a, c);
     bind_grid(a, c);
     bind_scale(a, c);
@@ -960,38 +906,31 @@ int orbgpu_fuse_batch(orbgpu_ctx* c, int n_pairs, const int32_t* frames, const i
     a.th = th;
     a.bf = gate ? bf : 0.0f;
     a.sim3 = !gate;
-    a.best_idx = c->fuseout.as<int32_t>();
-    a.best_dist = a.best_idx + rows;
-    a.code = reinterpret_cast<uint8_t*>(a.best_dist + rows);
-    a.first = c->fusefirst.as<uint32_t>();
-    a.nfused = c->fusenf.as<int32_t>();
     const int r = run_search(
-        c, stream,
-        [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->fusein.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-            if (total)
-                HIP_TRY(hipMemcpyAsync(c->fusept.p, pts + list_offsets[0], total * sizeof(FusePoint), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->fusepose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(c->fusefirst.p, 0xFF, np * cap * 4, s));  // -1: no point fused onto the keypoint
-            HIP_TRY(hipMemsetAsync(c->fusenf.p, 0, np * 4, s));
-            if (skip) return upload_rows(c->fuseskip.p, skip_pitch, skip, (size_t)skip_stride, (size_t)max_pts, np, 0, s);
-            return 0;
+        c, stream, res, "fuse", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            add_list_regions(ws, a, lp, np, skip != nullptr);
+            int32_t* first;  // the keypoint side is a match row: the lowest point that fused onto each keypoint
+            rs = add_match_rows(out, np, cap, first, a.nfused, nullptr, 0);
+            a.first = reinterpret_cast<uint32_t*>(first);
+            add_point_rows(out, rs, a, lp.rows);
         },
-        [&](hipStream_t s) { return launch_fuse(a, n_pairs, max_pts, s); });
-    if (r) return r;
-    set_cover(c->fuse_cover, np, frames, 1, false);
-    c->fuse_off.assign(head.begin() + 2 * np, head.begin() + 3 * np + 1);
-    return ORBGPU_OK;
+        [&](hipStream_t s) -> int {
+            HIP_TRY(hipMemsetAsync(a.first, 0xFF, np * cap * 4, s));  // -1: no point fused onto the keypoint
+            HIP_TRY(hipMemsetAsync(a.nfused, 0, np * 4, s));
+            return upload_list_inputs(a, lp, np, pts ? pts + list_offsets[0] : nullptr, poses, skip, skip_stride, s);
+        },
+        [&](hipStream_t s) { return launch_fuse(a, n_pairs, lp.max_pts, s); });
+    if (r == ORBGPU_OK) res.point_off.assign(lp.head.begin() + 2 * np, lp.head.begin() + 3 * np + 1);
+    return r;
 }
 
 int orbgpu_download_fuse_matches(orbgpu_ctx* c, int pair, int32_t* best_idx, int32_t* best_dist, uint8_t* code,
                                  int cap_points, int32_t* first, int cap_kp, int* n_points, int* n_kp, int* nfused) {
-    if (!c || pair < 0 || (size_t)pair >= c->fuse_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (!c || pair < 0 || (size_t)pair >= c->res[S_FUSE].cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
     // the keypoint side first: both counts are out before either capacity is judged
-    const int r = download_matches(c, c->fuse_cover, pair, "bad pair", c->fusefirst.as<int32_t>(), c->fusenf.as<int32_t>(),
-                                   row_cap(c, false), first, cap_kp, n_kp, nfused, nullptr);
-    return download_point_rows(c, c->fuse_off, pair, r, c->fuseout.as<int32_t>(), best_idx, best_dist, code, cap_points,
-                               n_points);
+    const int r = download_matches(c, c->res[S_FUSE], pair, "bad pair", first, cap_kp, n_kp, nfused, nullptr);
+    return download_point_rows(c, c->res[S_FUSE], pair, r, best_idx, best_dist, code, cap_points, n_points);
 }
 
 // ---- ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
@@ -1024,38 +963,15 @@ int orbgpu_sim3_search_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int
                                  [](int) { return 0; }))
         return e;
     if (n_pairs > 0 && kp_block && kp_stride < 0) return fail(ORBGPU_ERR_INVALID, "negative kp_stride");
-    if (n_pairs == 0) {
-        c->sim3_cover.image.clear();
-        c->sim3_off.clear();
-        return ORBGPU_OK;
-    }
-    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, total = (size_t)lp.total_pts;
+    SearchResult& res = c->res[S_SIM3];
+    if (n_pairs == 0) return no_results(res);
+    const size_t cap = (size_t)c->plan.out_cap, np = (size_t)n_pairs, rows = lp.rows;
     if (kp_block)  // one row of kp_stride flags per pair: it must cover the frame's keypoints
         if (int e = rows_cover_counts(c, c->grid_images, frames, 1, n_pairs, kp_stride,
                                       "kp_stride below the frame's keypoint count"))
             return e;
-    const std::vector<int32_t>& head = lp.head;
-    const size_t rows = lp.rows, skip_pitch = lp.skip_pitch;
     HIP_TRY(hipSetDevice(c->device));
-    // sim3out: best_idx, best_dist [rows each], code [rows] (the three download_point_rows reads), then,
-    // 4-byte aligned, the replay's order [rows]
-    const size_t order_at = (rows * 9 + 3) & ~(size_t)3;
-    if (c->sim3in.ensure(head.size() * 4 + 256) || c->sim3pt.ensure(total * sizeof(FusePoint) + 256) ||
-        c->sim3pose.ensure(np * sizeof(RelocPose) + 256) || (skip && c->sim3skip.ensure(np * skip_pitch + 256)) ||
-        (kp_block && c->sim3blk.ensure(np * cap + 256)) || c->sim3cand.ensure(rows * sizeof(RelocCand) + 256) ||
-        c->sim3out.ensure(order_at + rows * 4 + 256) || c->sim3match.ensure(np * cap * 4 + 256) ||
-        c->sim3nm.ensure(np * (1 + kSim3Stats) * 4 + 256))
-        return fail(ORBGPU_ERR_HIP, "hipMalloc failed (Sim3 projection search)");
     Sim3Args a{};
-    a.frames = c->sim3in.as<int32_t>();
-    a.lists = a.frames + np;
-    a.out_off = a.lists + np;
-    a.list_off = a.out_off + np + 1;
-    a.pts = c->sim3pt.as<FusePoint>();
-    a.poses = c->sim3pose.as<RelocPose>();
-    a.skip = skip ? c->sim3skip.as<uint8_t>() : nullptr;
-    a.skip_stride = (int)skip_pitch;
-    a.kp_block = kp_block ? c->sim3blk.as<uint8_t>() : nullptr;
     bind_frame(a, c);
     bind_grid(a, c);
     bind_scale(a, c);
@@ -1064,49 +980,38 @@ int orbgpu_sim3_search_by_projection_batch(orbgpu_ctx* c, int n_pairs, const int
     a.th = th;
     a.limit = limit;
     a.projection = projection;
-    a.cand = c->sim3cand.as<RelocCand>();
-    a.best_idx = c->sim3out.as<int32_t>();
-    a.best_dist = a.best_idx + rows;
-    a.code = reinterpret_cast<uint8_t*>(a.best_dist + rows);
-    a.order = reinterpret_cast<int32_t*>(c->sim3out.as<uint8_t>() + order_at);
-    a.match = c->sim3match.as<int32_t>();
-    a.nmatches = c->sim3nm.as<int32_t>();
-    a.stats = a.nmatches + np;
     const int r = run_search(
-        c, stream,
+        c, stream, res, "Sim3 projection search", cover_of(np, frames, 1, false),
+        [&](Layout& ws, Layout& out, ResultSlots& rs) {
+            add_list_regions(ws, a, lp, np, skip != nullptr);
+            a.kp_block = kp_block ? ws.add<uint8_t>(np * cap) : nullptr;
+            a.cand = ws.add<RelocCand>(rows);
+            a.order = ws.add<int32_t>(rows);  // the replay's own: no download reads it
+            rs = add_match_rows(out, np, cap, a.match, a.nmatches, &a.stats, kSim3Stats);
+            add_point_rows(out, rs, a, rows);
+        },
         [&](hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(c->sim3in.p, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
-            if (total)
-                HIP_TRY(hipMemcpyAsync(c->sim3pt.p, pts + list_offsets[0], total * sizeof(FusePoint), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c->sim3pose.p, poses, np * sizeof(RelocPose), hipMemcpyHostToDevice, s));
-            if (skip)
-                if (int e = upload_rows(c->sim3skip.p, skip_pitch, skip, (size_t)skip_stride, (size_t)lp.max_pts, np, 0, s))
-                    return e;
-            if (kp_block) return upload_rows(c->sim3blk.p, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), np, 0, s);
-            return 0;
+            if (int e = upload_list_inputs(a, lp, np, pts ? pts + list_offsets[0] : nullptr, poses, skip, skip_stride, s)) return e;
+            return upload_rows(a.kp_block, cap, kp_block, kp_stride, std::min((size_t)kp_stride, cap), np, 0, s);
         },
         [&](hipStream_t s) { return launch_sim3(a, n_pairs, lp.max_pts, s); });
-    if (r) return r;
-    set_cover(c->sim3_cover, np, frames, 1, false);
-    c->sim3_off.assign(head.begin() + 2 * np, head.begin() + 3 * np + 1);
-    return ORBGPU_OK;
+    if (r == ORBGPU_OK) res.point_off.assign(lp.head.begin() + 2 * np, lp.head.begin() + 3 * np + 1);
+    return r;
 }
 
 int orbgpu_download_sim3_matches(orbgpu_ctx* c, int pair, int32_t* match, int cap_kp, int32_t* best_idx,
                                  int32_t* best_dist, uint8_t* code, int cap_points, int* n_kp, int* n_points,
                                  int* nmatches) {
-    if (!c || pair < 0 || (size_t)pair >= c->sim3_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
-    const int r = download_matches(c, c->sim3_cover, pair, "bad pair", c->sim3match.as<int32_t>(), c->sim3nm.as<int32_t>(),
-                                   row_cap(c, false), match, cap_kp, n_kp, nmatches, nullptr);
-    return download_point_rows(c, c->sim3_off, pair, r, c->sim3out.as<int32_t>(), best_idx, best_dist, code, cap_points,
-                               n_points);
+    if (!c || pair < 0 || (size_t)pair >= c->res[S_SIM3].cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    const int r = download_matches(c, c->res[S_SIM3], pair, "bad pair", match, cap_kp, n_kp, nmatches, nullptr);
+    return download_point_rows(c, c->res[S_SIM3], pair, r, best_idx, best_dist, code, cap_points, n_points);
 }
 
 int orbgpu_sim3_replay_stats(orbgpu_ctx* c, int pair, int32_t stats[4]) {
     static_assert(kSim3Stats == 4, "the header states the count");
-    if (!c || !stats || pair < 0 || (size_t)pair >= c->sim3_cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
+    if (!c || !stats || pair < 0 || (size_t)pair >= c->res[S_SIM3].cover.image.size()) return fail(ORBGPU_ERR_INVALID, "bad pair");
     if (int e_ = ctx_sync(c)) return e_;
-    D2H(stats, c->sim3nm.as<int32_t>() + c->sim3_cover.image.size() + (size_t)pair * kSim3Stats, 4 * kSim3Stats);
+    D2H(stats, c->res[S_SIM3].at.hist + (size_t)pair * kSim3Stats, 4 * kSim3Stats);
     return ORBGPU_OK;
 }
 

@@ -1,7 +1,7 @@
 // host_harness.hip -- TEST INFRASTRUCTURE: runs the device algorithm headers of the product
 // (orb_octree.h, orb_fast_cell.h, orb_introsort.h, orb_math.h) on the host with SerialPolicy, and
-// the runtime's geometry planner (orb_geometry.h), so they can be checked against the CPU oracle
-// without a GPU.  Not part of liborbgpu.so.
+// the runtime's geometry planner (orb_geometry.h) and the matchers' buffer layout (orb_layout.h), so
+// they can be checked against the CPU oracle without a GPU.  Not part of liborbgpu.so.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -10,6 +10,7 @@
 #include "../../orbslam3lib_amd/csrc/orb_fast_cell.h"
 #include "../../orbslam3lib_amd/csrc/orb_geometry.h"
 #include "../../orbslam3lib_amd/csrc/orb_introsort.h"
+#include "../../orbslam3lib_amd/csrc/orb_layout.h"
 #include "../../orbslam3lib_amd/csrc/orb_math.h"
 #include "../../orbslam3lib_amd/csrc/orb_octree.h"
 #include "../../orbslam3lib_amd/csrc/orb_policy.h"
@@ -372,6 +373,30 @@ void harness_fast_launch_plan(int nimages, int fast_small, int n48, int n64, int
     const FastLaunchPlan p = fast_launch_plan(a, tile);
     const int32_t v[6] = {p.tile, p.c0, p.c1, p.small, p.ovf, 0};
     std::memcpy(out, v, sizeof(v));
+}
+
+// The matchers' Layout (orb_layout.h) over n slots in a buffer at `base` (0: sizing only), slot i of
+// counts[i] elements of elem_bytes[i] bytes (1, 2, 4, 8, 16, 44 or 60): addr[i] = the address add() gave
+// it.  Returns Layout::bytes, or -1 for an element size that is not instantiated here.
+long long harness_layout(unsigned long long base, int n, const long long* counts, const int32_t* elem_bytes,
+                         unsigned long long* addr) {
+    struct B44 { uint8_t b[44]; };
+    struct B60 { uint8_t b[60]; };
+    Layout lay{(uintptr_t)base};
+    for (int i = 0; i < n; ++i) {
+        const size_t k = (size_t)counts[i];
+        switch (elem_bytes[i]) {
+            case 1: addr[i] = (uintptr_t)lay.add<uint8_t>(k); break;
+            case 2: addr[i] = (uintptr_t)lay.add<int16_t>(k); break;
+            case 4: addr[i] = (uintptr_t)lay.add<int32_t>(k); break;
+            case 8: addr[i] = (uintptr_t)lay.add<double>(k); break;
+            case 16: addr[i] = (uintptr_t)lay.add<uint4>(k); break;
+            case 44: addr[i] = (uintptr_t)lay.add<B44>(k); break;
+            case 60: addr[i] = (uintptr_t)lay.add<B60>(k); break;
+            default: return -1;
+        }
+    }
+    return (long long)lay.bytes;
 }
 
 }  // extern "C"

@@ -319,3 +319,34 @@ def test_libm_fisheye_restatements_equal_host_libm(harness):
     g.argtypes = [C.c_longlong, C.c_ulonglong]
     assert g(2_000_000, 12345) == 0
 
+
+def test_matcher_layout_slots_are_aligned_apart_and_covered(harness):
+    """orb_layout.h, which carves the matchers' workspace and result buffers: over random slot lists of
+    mixed element sizes, some of them empty, every slot starts 256-byte aligned, is followed by at least
+    256 bytes that no other slot overlaps (so empty slots are distinct as well), and the size the layout
+    asks for covers the last slot and its slack.  The sizing pass (base 0) and the pass over a buffer
+    give the same offsets."""
+    f = harness.harness_layout
+    f.restype = C.c_longlong
+    f.argtypes = [C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    rng = np.random.default_rng(7)
+    sizes = np.array([1, 2, 4, 8, 16, 44, 60], np.int32)
+    for case in range(48):
+        n = int(rng.integers(1, 24))
+        elem = rng.choice(sizes, n).astype(np.int32)
+        counts = rng.integers(0, [3, 300, 70000][case % 3], n).astype(np.int64)
+        counts[rng.random(n) < 0.25] = 0
+        if case == 0:
+            counts[:] = 0
+        base = 0 if case % 2 else int(rng.integers(1, 1 << 20)) * 256
+        addr, off = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        total = f(base, n, _p(counts), _p(elem), _p(addr))
+        assert f(0, n, _p(counts), _p(elem), _p(off)) == total
+        np.testing.assert_array_equal(addr - np.uint64(base), off)
+        start = off.astype(np.int64)
+        end = start + counts * elem  # one past the slot's last byte
+        assert (start % 256 == 0).all()
+        assert start[0] == 0 and (start[1:] >= end[:-1] + 256).all(), (start, end)
+        assert total >= end[-1] + 256
+    bad = np.array([3], np.int32)
+    assert f(0, 1, _p(np.ones(1, np.int64)), _p(bad), _p(np.zeros(1, np.uint64))) == -1
